@@ -10,9 +10,12 @@ multiscale compose x2 -> inverse standardization -> multi-scale SMAPE loss -> fu
 for N>1) -> Adam.  Unit: 128x128 tile-passes per second, whole job.  bf16 storage / MFMA with fp32
 accumulate, fp32 master weights and optimizer state.  Weak scaling: per-GPU batch fixed.
 
-Rank 0 prints ONE JSON line (contract in the task statement) with `roofline` (dominant kernel = the MFMA implicit-GEMM
-conv, timed per launch with HIP events on the launch stream) and `cpu_baseline` (the CPU oracle -- a PyTorch-CPU restatement
-of the TensorFlow graph, TF itself is unavailable -- timed on a bounded sample of the same workload; rank 0, N=1 only).
+Rank 0 prints ONE JSON line (contract in the task statement).  A plain run sets up, warms up, times --steps steps and prints it;
+--full adds every secondary measurement: `roofline` (dominant kernel family, timed per launch with HIP events on the launch stream),
+`allreduce` (N>1), `extras` (inference, f32 path, cfg-3, example JSON, host inputs) and `cpu_baseline` (the CPU oracle -- a PyTorch-CPU
+restatement of the TensorFlow graph, TF itself is unavailable -- timed on a bounded sample of the same workload; rank 0, N=1 only).
+--dump-outputs DIR writes what the timed path computed in its last step to DIR/<name>.npy.  Inputs and weights are seeded and the last timed
+training step starts from the seeded state, so two runs with the same arguments write the same outputs up to the rounding of unordered reductions.
 """
 import argparse
 import json
@@ -28,6 +31,36 @@ sys.path.insert(0, ROOT)
 PEAK_BF16_TFLOPS = 2500.0      # dense MFMA peak, MI355X_MICROARCH.md
 PEAK_F32_TFLOPS = 157.3
 PEAK_HBM_GBS = 8000.0          # HBM3E, same guide
+
+
+DUMP_LIMIT = 60 << 20           # bytes of all --dump-outputs files together
+
+
+def dump_outputs(path, arrays, limit=DUMP_LIMIT):
+    """{name: tensor} -> path/<name>.npy in float32 (float64 stays float64).  When the arrays together would pass `limit` bytes, the limit is
+    shared out smallest array first: an array that fits in an equal share of what is left is written whole, each larger one as a fixed, seeded
+    sample of its flattened elements (the same indices in every run of the same arguments) of one equal share."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    esz = {k: 8 if v.dtype == torch.float64 else 4 for k, v in arrays.items()}
+    keep, left = {}, limit
+    pending = sorted(arrays, key=lambda k: arrays[k].numel() * esz[k])
+    while pending:
+        share = left // len(pending)
+        k = pending[0]
+        if arrays[k].numel() * esz[k] > share:
+            keep.update({n: max(1, share // esz[n]) for n in pending})
+            break
+        keep[k] = arrays[k].numel()
+        left -= arrays[k].numel() * esz[k]
+        pending.pop(0)
+    for name, v in arrays.items():
+        v = v.detach()
+        if keep[name] < v.numel():
+            idx = torch.randint(0, v.numel(), (keep[name],), generator=torch.Generator().manual_seed(0)).sort().values
+            v = v.reshape(-1)[idx.to(v.device)]
+        a = v.to(torch.float64 if esz[name] == 8 else torch.float32).cpu().numpy()
+        np.save(os.path.join(path, name.replace("/", "_") + ".npy"), a)
 
 
 def synthetic_inputs(arch, B, H, W, device, seed):
@@ -142,12 +175,12 @@ def cpu_baseline(aj, tj, H, W, budget_s=20.0):
                       "(oracle/; TensorFlow itself is not installable); thread count = best of a short sweep" % (n, B, H, W)}
 
 
-def inference_frames(device, dtype, tile, batch, steps, warmup, seed, buffer_sets=3, detail=None):
+def inference_frames(device, dtype, tile, batch, steps, warmup, seed, buffer_sets=3, detail=None, outputs=None):
     """Times `steps` full 1080x1920 frames through Predictor on this rank; returns seconds.  A frame SEQUENCE: the frames rotate through
     `buffer_sets` distinct sets of device tensors, so the per-frame upload of the input-assembly table runs (with one set it is skipped, as for a
     caller that refills its tensors in place).  detail (a dict): filled with the device-time breakdown of the timed frames (HIP events inside
     predict_frame): launches in front of the forward, the forward graph, stitch / recombination behind it, and the idle time BETWEEN frames
-    (device waiting for the host)."""
+    (device waiting for the host).  outputs (a dict): filled with what the last timed frame returned."""
     from deepdenoiser_amd import configs
     from deepdenoiser_amd.architecture import Architecture
     from deepdenoiser_amd.naming import Naming
@@ -165,9 +198,11 @@ def inference_frames(device, dtype, tile, batch, steps, warmup, seed, buffer_set
         pred.profile = []
     t0 = time.perf_counter()
     for i in range(steps):
-        pred.predict_frame(frames[i % len(frames)])
+        out = pred.predict_frame(frames[i % len(frames)])
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
+    if outputs is not None:
+        outputs.update(out)
     if detail is not None and pred.profile:
         ev = pred.profile
         n = len(ev)
@@ -183,7 +218,10 @@ def inference_bench(args, device, rank, world):
     """Full-frame inference: 1080x1920x32ch frame -> 209 halo tiles of 128^2 -> U-Net KPCN forward -> stitch.
     A step = one frame; every rank denoises its own frames (replicas only, no collective).  MPix/s counts OUTPUT pixels."""
     H, W = 1080, 1920
-    dt = inference_frames(device, args.dtype, args.tile, args.batch, args.steps, args.warmup, 7 + rank)
+    outputs = {} if args.dump_outputs and rank == 0 else None
+    dt = inference_frames(device, args.dtype, args.tile, args.batch, args.steps, args.warmup, 7 + rank, outputs=outputs)
+    if outputs:
+        dump_outputs(args.dump_outputs, outputs)
     if rank == 0:
         print(json.dumps({"metric": "inference MPix/s (1920x1080 frame, halo-tiled 128x128x32ch U-Net KPCN)", "value": world * args.steps * H * W / dt / 1e6,
                           "unit": "MPix/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": 1e3 * dt / args.steps,
@@ -357,9 +395,11 @@ def augment_bench(args, device, rank, world):
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        DataAugmentation.apply(feats, labels, draws, usage)
+        out_f, out_l = DataAugmentation.apply(feats, labels, draws, usage)
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {**out_f, **out_l})
     nbytes = 2 * 4 * sum(v.numel() for v in list(feats.values()) + list(labels.values()))
     if rank == 0:
         gbs = nbytes * args.steps / dt / 1e9
@@ -399,16 +439,23 @@ def main():
     ap.add_argument("--tile", type=int, default=128)
     ap.add_argument("--dtype", default=None, choices=["bf16", "f16", "f32"],
                     help="storage type (MFMA input type; accumulation is fp32): default bf16 for training, f16 for --mode inference (BASELINE config 5)")
-    ap.add_argument("--no-extras", action="store_true", help="skip the secondary measurements of the default line (inference MPix/s, f32-path tiles/s)")
+    ap.add_argument("--full", action="store_true", help="after the timed steps, also run every secondary measurement: the per-launch profiling "
+                                                        "pass (roofline), the all-reduce timing (N>1), the extras and the CPU baseline")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR", help="write what the timed path computed in its last step to DIR/<name>.npy "
+                                                                      "(float32, at most 64 MB in all: a fixed seeded sample of larger outputs)")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the secondary measurements of the default line (inference MPix/s, f32-path tiles/s)")
     ap.add_argument("--no-graph", action="store_true", help="do not capture the step into a hipGraph")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--mode", default="train", choices=["train", "inference", "augment"],
                     help="inference: full-frame 1920x1080 halo-tiled prediction (BASELINE config 5), reported as MPix/s -- a secondary line, "
                          "the driver's contract is the default train mode")
-    ap.add_argument("--dump-launches", default="", help="write the per-launch records of the profiling pass (family, shape, flops, us) to this JSON file")
+    ap.add_argument("--dump-launches", default="", help="write the per-launch records of the profiling pass (family, shape, flops, us) to this JSON file "
+                                                        "(runs the profiling pass without --full too)")
     ap.add_argument("--host-inputs", action="store_true",
                     help="PCIe-inclusive variant (NOT the headline value): every step first copies its batch from pinned host memory")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     if args.batch is None:
         args.batch = 256 if args.mode == "inference" else 128
@@ -469,18 +516,35 @@ def main():
         stager = trainer.program.host_stager()
         stager.stage(hf, hl)
 
-        def one_step():
+        def feed():
             stager.consume()
             stager.stage(hf, hl)
-            trainer.step()
     else:
-        one_step = trainer.step
+        feed = None
+
+    def one_step():
+        if feed is not None:
+            feed()
+        trainer.step()
+
+    # The LAST timed step starts from the seeded state (weights, Adam moments and step count), so what it computes depends on the seeded inputs
+    # alone.  The weight and bias gradients end in fp32 atomics whose order changes from run to run; over continued training those last-bit
+    # differences grow through Adam and the bf16 operand rounding (~5e-3 rel-L2 in the weights after 25 steps), from the seeded state two runs
+    # agree to rounding.  Only that one step: this network runs ~4 % slower at its seeded weights than after a few steps of training.
+    ps = arch.params
+    seeded = [t.clone() for t in (ps.values, ps.m, ps.v)]
+
+    def reseed():
+        torch._foreach_copy_([ps.values, ps.m, ps.v], seeded)
+        arch.adam_step = 0
 
     for _ in range(args.warmup):
         one_step()
     barrier()
     t0 = time.perf_counter()
-    for _ in range(args.steps):
+    for i in range(args.steps):
+        if i == args.steps - 1:
+            reseed()
         one_step()
     barrier()
     dt = time.perf_counter() - t0
@@ -489,15 +553,18 @@ def main():
         t = torch.tensor([dt], device=device, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t)
+    # ---- what the last timed step hands its caller: the loss it returns and the fp32 weights after its Adam update
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"loss": trainer.program.loss_buf, "params": arch.params.values})
 
     # ---- the gradient all-reduces of a step on their side stream, and the part the launch stream waited for (every rank runs these steps)
-    coll = trainer.measure_collectives(5) if use_dist else None
+    coll = trainer.measure_collectives(5) if use_dist and args.full else None
     if use_dist:
         barrier()
 
     # ---- roofline of the dominant kernel: per-launch HIP-event timing on the launch stream (outside the timed region)
     roof = None
-    if rank == 0:
+    if rank == 0 and (args.full or args.dump_launches):
         times, launches = trainer.program.profile_ops(detail=True)           # {kernel family: (launches, total_ms, flops)}, per-launch records
         if args.dump_launches:
             # every launch of the step in program order: family, shape record (B, H, W, taps, n = C_out, k = C_in, flops, flags), HIP-event us --
@@ -572,17 +639,19 @@ def main():
             # physical devices behind the ranks: == n_gpus except under the DD_FORCE_DEVICE test hook (several ranks sharing one GPU)
             "devices": 1 if os.environ.get("DD_FORCE_DEVICE") else world,
             "collectives": (os.environ.get("DD_DIST_BACKEND", "nccl") if use_dist else None),
-            # per step: time of the bucketed gradient all-reduces on the side stream and how much of it was NOT hidden behind the backward
-            "allreduce": coll,
             "config": {"workload": "BASELINE config 2: U-Net [64,96,128]x4 + 5x5 KernelPrediction + 3-scale MultiScalePrediction, "
                                    "32-channel render-pass stack, %dx%d tiles, full training step (fwd+SMAPE loss+bwd+Adam)" % (H, W),
                        "tiles_per_gpu_per_step": B, "global_batch": world * B, "parallelism": "dp%d" % world,
                        "hipgraph": not args.no_graph, "final_loss": loss,
                        # a tile of the reference's example JSON is 17 SINGLE tuple passes through the network
                        "example_json_tiles_per_s": world * B * args.steps / dt / 17.0, "inputs": "pinned host, copied every step" if args.host_inputs else "resident in HBM"},
-            "roofline": roof,
         }
-        if world == 1 and not args.no_extras:
+        if args.full:
+            # per step: time of the bucketed gradient all-reduces on the side stream and how much of it was NOT hidden behind the backward
+            out["allreduce"] = coll
+        if roof is not None:
+            out["roofline"] = roof
+        if world == 1 and args.full and not args.no_extras:
             out["extras"] = extras(device, B, H, W)
             if not args.host_inputs:
                 # the same step fed from pinned host memory every step (PCIe-inclusive; never `value`): double-buffered staging on a copy stream
@@ -603,7 +672,7 @@ def main():
                                                 "frac_of_resident": (B * args.steps / dth) / out["value"],
                                                 "bytes_per_step": sum(v.numel() * v.element_size() for v in list(hf.values()) + list(hl.values())),
                                                 "inputs": "pinned host fp32, copied every step on a copy stream (2 staging slots), then device-to-device into the program's buffers"}
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(aj, tj, H, W)
         print(json.dumps(out))
     if use_dist:

@@ -19,7 +19,7 @@ for rep in range(repeat):
         for kv in filter(None, envs.split(",")):
             k, _, v = kv.partition("=")
             env[k] = v
-        out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--no-extras", "--no-cpu-baseline"] + mode, env=env, capture_output=True, text=True)
+        out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--no-extras", "--no-cpu-baseline"] + mode, env=env, capture_output=True, text=True)
         line = [l for l in out.stdout.splitlines() if l.startswith("{")]
         if not line:
             print(name, "FAILED", out.stderr[-2000:])

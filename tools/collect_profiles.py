@@ -21,7 +21,7 @@ for name in ("bench.json", "kernel_stats.txt", "inference.json", "host_inputs.tx
         if name == "kernel_stats.txt":
             bench = json.loads(open(os.path.join(src, "bench.json")).read().strip().splitlines()[-1])
             with open(out, "w") as f:
-                f.write("# %s: rocprofv3 --kernel-trace --stats of `python bench.py --no-cpu-baseline --no-extras` (cfg-2, bf16, B=128 tiles of 128x128 per GPU, hipGraph;\n"
+                f.write("# %s: rocprofv3 --kernel-trace --stats of `python bench.py --full --no-cpu-baseline --no-extras` (cfg-2, bf16, B=128 tiles of 128x128 per GPU, hipGraph;\n"
                         "#   5 warm-up + 20 timed steps + 4 per-op timing passes = 29 step-equivalents).  %s\n"
                         "# bench line of the same build without profiler: profiles/%s_bench.json (%.0f tiles/s)\n" % (tag, note, tag, bench["value"]))
                 f.write(open(p).read())
@@ -52,7 +52,7 @@ def family(path):
 
 
 fetch, write = family(os.path.join(src, "pmc_FETCH_SIZE.txt")), family(os.path.join(src, "pmc_WRITE_SIZE.txt"))
-traffic = {"how": "rocprofv3 --pmc FETCH_SIZE and --pmc WRITE_SIZE in separate passes (no trace options) over `python bench.py --no-cpu-baseline "
+traffic = {"how": "rocprofv3 --pmc FETCH_SIZE and --pmc WRITE_SIZE in separate passes (no trace options) over `python bench.py --full --no-cpu-baseline "
                   "--no-extras --no-graph --steps 2 --warmup 1` (7 step-equivalents); mean per dispatch of the kernel family (tools/pmc_family.py; "
                   "raw: profiles/%s_pmc_*.txt, values in kB).  FETCH_SIZE doubled per MI355X_MICROARCH.md (gfx950 tallies 128-B requests at 64 B); "
                   "WRITE_SIZE uncorrected (calibrated in round 1 on a 64->64 forward launch: 67.3 MB counted for 67.1 MB written)." % tag,

@@ -3,7 +3,7 @@
 #   SQT_CMD="python tools/cfg3_step.py heavy 8 2" SQT_OUT=gpurun_out/sq_table_cfg3_heavy.txt tools/pmc_sq_table.sh conv_ks wgrad conv_igemm_ws conv_pw   (another workload)
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 out=gpurun_out/pmc_sqt
-cmd=${SQT_CMD:-python bench.py --no-cpu-baseline --no-extras --no-graph --steps 2 --warmup 1}
+cmd=${SQT_CMD:-python bench.py --full --no-cpu-baseline --no-extras --no-graph --steps 2 --warmup 1}
 res=${SQT_OUT:-gpurun_out/pmc_sq_table.txt}
 rm -rf $out; mkdir -p $out
 timeout 600 rocprofv3 --pmc SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_WAIT_INST_LDS SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_LDS SQ_ACTIVE_INST_SCA -d $out/p1 -o pmc --output-format csv -- $cmd > $out/log1.txt 2>&1
