@@ -24,6 +24,7 @@ SYMBOLS = (
     "dd_augment", "dd_loss_mask_sums", "dd_crc32c", "dd_extract_tiles", "dd_compose_net_fwd", "dd_compose_net_bwd",
     "dd_kpcn_head_fwd", "dd_kpcn_head_bwd", "dd_kpcn_head_bwd_multi", "dd_assemble_input", "dd_assemble_input_frames", "dd_conv3x3_bwd", "dd_conv3x3_bwd_multi", "dd_convt2x2_fwd", "dd_convt2x2_bwd", "dd_conv3x3_ks",
     "dd_conv_pw_count", "dd_wgrad_pw_count", "dd_space_to_depth2", "dd_convt3_wgrad", "dd_compose_stream_plan", "dd_compose_bwd_scratch_bytes",
+    "dd_loss_msssim_scratch_bytes", "dd_loss_msssim_fwd", "dd_loss_msssim_bwd",
 )
 
 
@@ -124,6 +125,17 @@ class LossDesc(C.Structure):
                 ("mask_sums", C.c_void_p),
                 ("pred_std", C.c_void_p * MAX_FEATURES), ("pred_inv", C.c_void_p * MAX_FEATURES),
                 ("inv_log1p", C.c_int * MAX_FEATURES), ("inv_mean", C.c_float * MAX_FEATURES), ("inv_std", C.c_float * MAX_FEATURES)]
+
+
+class MsSsimDesc(C.Structure):      # dd_loss_msssim_desc
+    _fields_ = [("n_features", C.c_int),
+                ("pred", C.c_void_p * MAX_FEATURES), ("target", C.c_void_p * MAX_FEATURES), ("dpred", C.c_void_p * MAX_FEATURES),
+                ("target_ld", C.c_int * MAX_FEATURES), ("pred_ld", C.c_int * MAX_FEATURES), ("nch", C.c_int * MAX_FEATURES),
+                ("ssim_weight", C.c_float * MAX_FEATURES),
+                ("n_combined", C.c_int), ("comb", (C.c_int * 3) * MAX_COMBINED), ("comb_ssim_weight", C.c_float * MAX_COMBINED),
+                ("n_image_combined", C.c_int), ("image_combined", C.c_int * MAX_COMBINED),
+                ("n_image_features", C.c_int), ("image_features", C.c_int * MAX_FEATURES),
+                ("image_ssim_weight", C.c_float)]
 
 
 class AugmentDraw(C.Structure):
@@ -250,6 +262,10 @@ def load():
     lib.dd_invert_std_fwd.argtypes = [vp, vp, l, i, f, f, vp]
     lib.dd_invert_std_bwd.argtypes = [vp, vp, vp, l, i, f, f, vp]
     lib.dd_loss_head.argtypes = [C.POINTER(LossDesc), i, i, i, vp, f, vp]
+    lib.dd_loss_msssim_scratch_bytes.argtypes = [i, i, i, i]
+    lib.dd_loss_msssim_scratch_bytes.restype = C.c_long
+    lib.dd_loss_msssim_fwd.argtypes = [C.POINTER(MsSsimDesc), i, i, i, vp, vp, vp]
+    lib.dd_loss_msssim_bwd.argtypes = [C.POINTER(MsSsimDesc), i, i, i, vp, f, vp]
     lib.dd_adam_step.argtypes = [vp, vp, vp, vp, l, f, f, f, f, f, vp]
     lib.dd_stitch.argtypes = [vp, i, i, vp, i, i, i, i, vp, i, vp]
     lib.dd_recombine.argtypes = [C.POINTER(RecombineDesc), l, vp]

@@ -95,14 +95,15 @@ def cfg3_tiramisu(filters=(16, 24, 32), convs=4):
 
 def training(learning_rate=1e-3, batch_size=8, loss_difference="SMAPE", multiscale_loss=True,
              feature_mean=1.0, combined_mean=5.0, image_mean=10.0, feature_variation=0.0, masked_mean=0.0,
-             combined_variation=0.0, image_variation=0.0, combined_masked_mean=0.0):
-    """Content-equivalent of the reference's TrainingExample.json (defaults) with a few knobs."""
+             combined_variation=0.0, image_variation=0.0, combined_masked_mean=0.0, ms_ssim=(0.0, 0.0, 0.0)):
+    """Content-equivalent of the reference's TrainingExample.json (defaults) with a few knobs.  ms_ssim: the ms_ssim weights of the
+    (features, combined features, combined image) levels."""
     stats = {"track_mean": True, "track_variation": False, "track_ms_ssim": False,
              "track_difference_histogram": False, "track_variation_difference_histogram": False}
     stats_off = dict(stats, track_mean=False)
 
-    def w(mean, variation=0.0):
-        return {"mean": mean, "variation": variation, "ms_ssim": 0.0}
+    def w(mean, variation=0.0, ms_ssim=0.0):
+        return {"mean": mean, "variation": variation, "ms_ssim": float(ms_ssim)}
 
     return {
         "architecture": "ArchitectureExample.json",
@@ -116,11 +117,11 @@ def training(learning_rate=1e-3, batch_size=8, loss_difference="SMAPE", multisca
         "loss_difference": loss_difference,
         "use_multiscale_loss": multiscale_loss,
         "use_multiscale_metrics": True,
-        "combined_image_training_settings": {"loss_weights": w(image_mean, image_variation), "statistics": dict(stats if image_mean > 0 else stats_off)},
-        "combined_features_training_settings": {"loss_weights": w(combined_mean, combined_variation), "loss_weights_masked": w(combined_masked_mean),
+        "combined_image_training_settings": {"loss_weights": w(image_mean, image_variation, ms_ssim[2]), "statistics": dict(stats if image_mean > 0 else stats_off)},
+        "combined_features_training_settings": {"loss_weights": w(combined_mean, combined_variation, ms_ssim[1]), "loss_weights_masked": w(combined_masked_mean),
                                                 "statistics": dict(stats if combined_mean > 0 else stats_off),
                                                 "statistics_masked": dict(stats_off)},
-        "features_training_settings": {"loss_weights": w(feature_mean, feature_variation), "loss_weights_masked": w(masked_mean),
+        "features_training_settings": {"loss_weights": w(feature_mean, feature_variation, ms_ssim[0]), "loss_weights_masked": w(masked_mean),
                                        "statistics": dict(stats), "statistics_masked": dict(stats_off)},
     }
 

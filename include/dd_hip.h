@@ -386,6 +386,45 @@ int dd_loss_mask_sums(const dd_loss_desc* desc, int B, int H, int W, float* mask
 /* loss_out[0] += total weighted loss of this scale; dpred written. desc is a HOST struct (copied by value). */
 int dd_loss_head(const dd_loss_desc* desc, int B, int H, int W, float* loss_out, float grad_scale, dd_stream stream);
 
+/* ---- MS-SSIM loss term (BaseFeatureTraining.ms_ssim Training.py:178-204, added ONCE with ms_ssim_weight alone at Training.py:231-232: no
+ * multi-scale scale factor, always on predicted[0] / target[0]; tf.image.ssim_multiscale with max_val 1 and the THREE power factors
+ * (0.0448, 0.2856, 0.3001), filter 11 x 11, sigma 1.5, k1 0.01, k2 0.03):
+ *   term = weight * (1 - mean over images of MS),   MS = mean over channels of relu(cs_0)^0.0448 relu(cs_1)^0.2856 relu(ssim_2)^0.3001,
+ * level k > 0 = the 2x2 / stride-2 average pool of level k-1, cs_k / ssim_k the means over the (h-10)(w-10) VALID filter positions.
+ * The descriptor names the SOURCES of one scale-0 evaluation: a feature (FeatureTraining Training.py:374-392), a combined feature
+ * color * (direct + indirect) (CombinedFeatureTraining.initialize Training.py:420-437) and the combined image = sum of its members
+ * (CombinedImageFeatureTraining.initialize Training.py:475-495); every source with a positive weight is evaluated.  All tensors fp32 NHWC,
+ * all arithmetic fp32.  Every used feature needs nch == 3 (Training.py:187-190 transposes anything else into an image 1 pixel high).
+ * Every reduction has a fixed order (no atomics): loss and gradient are bit-identical from run to run.
+ * Where relu clamps a factor (cs_k <= 0, an anti-correlated pair) MS of that image and channel is 0 as in TensorFlow; TensorFlow's own
+ * gradient there is 0 * inf, OURS IS DEFINED AS 0 for that image and channel (finite).  A NaN in pred or target is NOT clamped away: it
+ * reaches MS, loss_out and the gradient of that image and channel as in TensorFlow (a diverged run shows in the loss).
+ * H and W must be multiples of 4 with min(H, W) / 4 >= 11 (TF refuses a level smaller than its filter; odd levels would need its symmetric pad). */
+typedef struct {
+  int n_features;
+  const float* pred[DD_MAX_FEATURES];    /* [B,H,W,pred_ld], as dd_loss_desc */
+  const float* target[DD_MAX_FEATURES];  /* [B,H,W,target_ld] */
+  float* dpred[DD_MAX_FEATURES];         /* [B,H,W,3], ADDED to by dd_loss_msssim_bwd; NULL: no gradient wanted (a generated pass) */
+  int target_ld[DD_MAX_FEATURES];
+  int pred_ld[DD_MAX_FEATURES];
+  int nch[DD_MAX_FEATURES];
+  float ssim_weight[DD_MAX_FEATURES];    /* ms_ssim weight of the feature's own term; 0: none */
+  int n_combined;
+  int comb[DD_MAX_COMBINED][3];          /* feature indices of color, direct, indirect */
+  float comb_ssim_weight[DD_MAX_COMBINED];
+  int n_image_combined; int image_combined[DD_MAX_COMBINED];   /* indices into comb[] */
+  int n_image_features; int image_features[DD_MAX_FEATURES];   /* indices into features */
+  float image_ssim_weight;
+} dd_loss_msssim_desc;
+/* bytes of the scratch buffer (pooled levels, coarse gradients, per-tile partial sums, coefficients) for n_sources = the number of sources
+ * with a positive weight; negative dd_status on a bad shape */
+long dd_loss_msssim_scratch_bytes(int B, int H, int W, int n_sources);
+/* loss_out[0] += sum of the weighted terms; leaves in scratch what dd_loss_msssim_bwd needs.  desc is a HOST struct.  No host sync. */
+int dd_loss_msssim_fwd(const dd_loss_msssim_desc* desc, int B, int H, int W, float* scratch, float* loss_out, dd_stream stream);
+/* dpred += grad_scale * d term / d pred, routed through the combined product (d color += g (direct + indirect), d direct += g color,
+ * d indirect += g color) and the image sum.  Same desc / scratch as the forward it follows on the same stream. */
+int dd_loss_msssim_bwd(const dd_loss_msssim_desc* desc, int B, int H, int W, float* scratch, float grad_scale, dd_stream stream);
+
 /* ---- Adam, TensorFlow formulation (tf.train.AdamOptimizer, Training.py:701-702), flat arenas */
 int dd_adam_step(float* params, const float* grads, float* m, float* v, long n, float lr_t, float beta1, float beta2,
                  float eps, float grad_scale, dd_stream stream);
