@@ -13,6 +13,7 @@ LIB_PATH = os.environ.get("DD_LIB", os.path.join(_HERE, "libdd_hip.so"))   # DD_
 DD_F32, DD_BF16, DD_F16 = 0, 1, 2
 IN_RELU, OUT_RELU, ACCUM, PIXSHUF, GATHER2X2 = 1, 2, 4, 8, 16
 MAX_FEATURES, MAX_COMBINED = 32, 8
+METRIC_SOURCES = MAX_FEATURES + MAX_COMBINED + 1      # DD_METRIC_SOURCES: rows of the dd_loss_metrics table per image
 
 # every symbol include/dd_hip.h declares (checked by tests/test_abi.py)
 SYMBOLS = (
@@ -24,7 +25,8 @@ SYMBOLS = (
     "dd_augment", "dd_loss_mask_sums", "dd_crc32c", "dd_extract_tiles", "dd_compose_net_fwd", "dd_compose_net_bwd",
     "dd_kpcn_head_fwd", "dd_kpcn_head_bwd", "dd_kpcn_head_bwd_multi", "dd_assemble_input", "dd_assemble_input_frames", "dd_conv3x3_bwd", "dd_conv3x3_bwd_multi", "dd_convt2x2_fwd", "dd_convt2x2_bwd", "dd_conv3x3_ks",
     "dd_conv_pw_count", "dd_wgrad_pw_count", "dd_space_to_depth2", "dd_convt3_wgrad", "dd_compose_stream_plan", "dd_compose_bwd_scratch_bytes",
-    "dd_loss_msssim_scratch_bytes", "dd_loss_msssim_fwd", "dd_loss_msssim_bwd",
+    "dd_loss_msssim_scratch_bytes", "dd_loss_msssim_fwd", "dd_loss_msssim_bwd", "dd_loss_msssim_values",
+    "dd_loss_metrics_scratch_bytes", "dd_loss_metrics",
 )
 
 
@@ -266,6 +268,10 @@ def load():
     lib.dd_loss_msssim_scratch_bytes.restype = C.c_long
     lib.dd_loss_msssim_fwd.argtypes = [C.POINTER(MsSsimDesc), i, i, i, vp, vp, vp]
     lib.dd_loss_msssim_bwd.argtypes = [C.POINTER(MsSsimDesc), i, i, i, vp, f, vp]
+    lib.dd_loss_msssim_values.argtypes = [C.POINTER(MsSsimDesc), i, i, i, vp, vp, vp]
+    lib.dd_loss_metrics_scratch_bytes.argtypes = [i, i, i]
+    lib.dd_loss_metrics_scratch_bytes.restype = C.c_long
+    lib.dd_loss_metrics.argtypes = [C.POINTER(LossDesc), i, i, i, vp, vp, vp]
     lib.dd_adam_step.argtypes = [vp, vp, vp, vp, l, f, f, f, f, f, vp]
     lib.dd_stitch.argtypes = [vp, i, i, vp, i, i, i, i, vp, i, vp]
     lib.dd_recombine.argtypes = [C.POINTER(RecombineDesc), l, vp]

@@ -239,6 +239,15 @@ __global__ __launch_bounds__(NTHREADS) void msssim_total_kernel(MsArgs a, float*
   if (tid == 0) loss_out[0] += total;
 }
 
+// ---------------------------------------------------------------------------------------------------------------- tracked values
+// ms_out[s * B + b] = MS of source s, image b: the mean over the channels of what msssim_coef_kernel left (fixed order)
+__global__ __launch_bounds__(64) void msssim_values_kernel(MsArgs a, float* __restrict__ ms_out) {
+  const int i = blockIdx.x * 64 + threadIdx.x;
+  if (i >= a.n_src * a.B) return;
+  const float* c = a.coef + (long)i * 3 * 4;
+  ms_out[i] = ((c[3] + c[7]) + c[11]) / 3.f;
+}
+
 // ---------------------------------------------------------------------------------------------------------------- backward
 __device__ __forceinline__ void add_to(float* p, long o, float v) {
   if (p) p[o] += v;
@@ -502,6 +511,22 @@ extern "C" int dd_loss_msssim_fwd(const dd_loss_msssim_desc* desc, int B, int H,
   hipLaunchKernelGGL(msssim_coef_kernel, dim3((a.n_src * B * 3 + 63) / 64), dim3(64), 0, st, a);
   DD_LAUNCH_CHECK();
   hipLaunchKernelGGL(msssim_total_kernel, dim3(1), dim3(NTHREADS), 0, st, a, loss_out);
+  DD_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int dd_loss_msssim_values(const dd_loss_msssim_desc* desc, int B, int H, int W, float* scratch, float* ms_out, dd_stream stream) {
+  DD_REQUIRE(ms_out != nullptr, "dd_loss_msssim_values: null ms_out");
+  MsArgs a;
+  int kinds[3];
+  if (int e = make_args(desc, B, H, W, scratch, a, kinds)) return e;
+  hipStream_t st = (hipStream_t)stream;
+  if (int e = launch_fwd<0>(a, st)) return e;
+  if (int e = launch_fwd<1>(a, st)) return e;
+  if (int e = launch_fwd<2>(a, st)) return e;
+  hipLaunchKernelGGL(msssim_coef_kernel, dim3((a.n_src * B * 3 + 63) / 64), dim3(64), 0, st, a);
+  DD_LAUNCH_CHECK();
+  hipLaunchKernelGGL(msssim_values_kernel, dim3((a.n_src * B + 63) / 64), dim3(64), 0, st, a, ms_out);
   DD_LAUNCH_CHECK();
   return 0;
 }

@@ -9,7 +9,11 @@ mini-batches and each takes every world-th one; an epoch is cut to a multiple of
 steps (and collectives).  `--validate` is a validation-only run; otherwise every `--validation_interval` epochs are followed by a validation
 pass over base/validation/<spp>/ for every validation*.json (Training.py:1230-1284).
 
-Not reproduced (out of scope): the Estimator's evaluation / TensorBoard summaries; validation reports the mean loss."""
+Summaries (metrics.py, summaries.py): every `--summary_steps` steps (100 = the Estimator's save_summary_steps, Training.py:1214) rank 0 writes
+`loss`, `learning_rate`, `batch_size` (Training.py:676-677) and the tracked scalars of Training.json's statistics sections (Training.py:688-698)
+for the current mini-batch into a TensorBoard event file in the model directory; a validation pass averages the same metrics over the
+validation set (eval_metric_ops, Training.py:704-719), prints them and writes them with `loss` into <model_directory>/eval_<validation json stem>/
+(estimator.evaluate(name=...), Training.py:874-877).  Not reproduced: histogram and image summaries."""
 import argparse
 import json
 import multiprocessing
@@ -22,9 +26,10 @@ import time
 import numpy as np
 import torch
 
-from . import tf_checkpoint, tfrecords
+from . import summaries, tf_checkpoint, tfrecords
 from .architecture import Architecture
 from .data_augmentation import DataAugmentation, DataAugmentationUsage
+from .metrics import MeanAccumulator
 from .naming import Naming
 from .tiling import source_index_tuples
 from .training import Trainer
@@ -40,6 +45,8 @@ def parser():
     p.add_argument("--data_format", type=str, default="channels_first", choices=["channels_first", "channels_last"],
                    help="Accepted for compatibility: the MI355X path is NHWC-native, both values give the same results.")
     p.add_argument("--dtype", default="bf16", choices=["bf16", "f16", "f32"], help="storage type of activations (accumulation is fp32)")
+    p.add_argument("--summary_steps", type=int, default=100,
+                   help="Write the loss and the tracked metrics of the current mini-batch as TensorBoard scalars every this many steps (0: never).")
     p.add_argument("--seed", type=int, default=0, help="seed of the file / example shuffles and of the source index tuples (shared by all ranks)")
     return p
 
@@ -226,10 +233,13 @@ class Uploader:
         return df, dl, done, (feats, labels)                            # (the pinned sources stay alive until the copy has run)
 
 
-def run_validation(trainer, arch, tj, base, B, rank, world, threads):
-    """Training.py:1230-1250 / :1264-1284: every validation*.json, tiles of base/validation/<spp>/, no augmentation, mean loss."""
+def run_validation(trainer, arch, tj, base, B, rank, world, threads, metrics_out=None):
+    """Training.py:1230-1250 / :1264-1284: every validation*.json, tiles of base/validation/<spp>/, no augmentation, mean loss.
+    metrics_out: a dict that receives {validation json stem: [(metric name, mean over the set)]} -- the tracked metrics of every mini-batch
+    (program.metrics over its real examples), averaged with the weights the loss gets."""
     import torch.distributed as dist
     results = []
+    plan = trainer.program.metric_plan() if metrics_out is not None else []
     for name in evaluation_jsons(base, "validation"):
         st = json.load(open(os.path.join(base, name), encoding="utf-8"))
         spp = st["source_samples_per_pixel_list"][0]
@@ -243,12 +253,14 @@ def run_validation(trainer, arch, tj, base, B, rank, world, threads):
             continue
         stream = TileStream(vdir, "validation", arch, B, st["tiles_height_width"], spp, tuples, rank, world, rng=None, threads=threads, pad_last=True)
         total = torch.zeros(2, dtype=torch.float64, device=arch.device)
-        losses = []
+        losses, tables = [], []
         for feats, labels in stream:
             trainer.program.set_inputs({k: v.to(arch.device) for k, v in feats.items()}, {k: v.to(arch.device) for k, v in labels.items()})
             trainer.program.zero_grads()
             trainer.program.forward()
             losses.append(trainer.program.loss_buf.double().sum())
+            if plan:      # (a copy on the device: how many of the LAST mini-batch are real is known only when the stream has ended)
+                tables.append(trainer.program.metric_table().clone())
         # every example counts once: a mini-batch's mean is weighed by its REAL examples (the last round of the epoch is filled with repeats)
         for i, l in enumerate(losses):
             w = stream.real_in_last if (stream.padded and i == len(losses) - 1) else B
@@ -256,6 +268,18 @@ def run_validation(trainer, arch, tj, base, B, rank, world, threads):
             total[1] += w
         if world > 1:
             dist.all_reduce(total)
+        if plan:
+            acc = MeanAccumulator(len(plan))
+            for i, t in enumerate(tables):
+                w = stream.real_in_last if (stream.padded and i == len(tables) - 1) else B
+                if w > 0:      # repeated examples do not count
+                    acc.add(trainer.program.metric_values(t, real=w), w)
+            if world > 1:
+                state = torch.from_numpy(acc.state()).to(arch.device)
+                dist.all_reduce(state)
+                acc.from_state(state.cpu().numpy())
+            if acc.weight > 0:
+                metrics_out[os.path.splitext(name)[0]] = list(zip([e.name for e in plan], acc.result()))
         if float(total[1]) > 0:
             results.append((os.path.splitext(name)[0], float(total[0] / total[1]), int(total[1])))
             if stream.padded and rank == 0:
@@ -289,16 +313,47 @@ def main(args):
         print("restored %s (global_step %d)" % (latest, step))
     validate = "validation" in tj["modes"]
 
+    eval_writers = {}
+
     def report_validation(tag):
-        for name, loss, n in run_validation(trainer, arch, tj, base, B, rank, world, args.threads):
+        tracked = {}
+        for name, loss, n in run_validation(trainer, arch, tj, base, B, rank, world, args.threads, metrics_out=tracked):
             if rank == 0:
                 print("%s: %s loss %.5f over %d batches" % (tag, name, loss, n))
+                for metric, value in tracked.get(name, []):
+                    print("%s: %s %s %.6g" % (tag, name, metric, value))
+                if name not in eval_writers:      # estimator.evaluate(name=name): one event file per run and validation set
+                    eval_writers[name] = summaries.EventFileWriter(os.path.join(model_dir, "eval_" + name))
+                eval_writers[name].add_scalars(step, [("loss", loss)] + tracked.get(name, []))
 
     if args.validate:                                                     # Training.py:1230: a validation-only run
         report_validation("validation")
+        for w in eval_writers.values():
+            w.close()
         if dist is not None:
             dist.destroy_process_group()
         return
+
+    writer = summaries.EventFileWriter(model_dir) if (rank == 0 and args.summary_steps > 0) else None
+    names = [e.name for e in trainer.program.metric_plan()] if args.summary_steps > 0 else []
+
+    def tracked_scalars():
+        """The tracked metrics of the staged mini-batch at the current weights: a forward of its own BEFORE trainer.step() (the step is left
+        as it is, and its backward may reuse prediction buffers).  Under data parallelism the per-image sums of all ranks are added, so
+        rank 0 logs the global batch."""
+        if not names:
+            return []
+        prog = trainer.program
+        prog.zero_grads()
+        prog.forward()
+        table = prog.metric_table()
+        if world == 1:
+            return list(zip(names, prog.metric_values(table)))
+        st = prog._metrics_built()
+        n = len(st["scales"]) * st["rows"]
+        sums = torch.cat([table[:n].double().reshape(-1, B, 4).sum(dim=1).reshape(-1), table[n:].double().reshape(-1, B).sum(dim=1)])
+        dist.all_reduce(sums)
+        return list(zip(names, prog.metric_values(sums.cpu().numpy(), count=world * B)))
 
     usage = DataAugmentationUsage.from_training_json(tj)
     gen = torch.Generator().manual_seed(1234 + rank)
@@ -324,8 +379,17 @@ def main(args):
             trainer.program.set_inputs(feats, labels)
             nxt = next(it, None)                                         # the next mini-batch uploads while this step runs
             staged = uploader.stage(*nxt) if nxt is not None else None
+            summary = args.summary_steps > 0 and (step + 1) % args.summary_steps == 0
+            scalars = tracked_scalars() if summary else None
             loss = trainer.step()
             step += 1
+            if summary:
+                mean_loss = loss.double().sum()
+                if dist is not None:
+                    dist.all_reduce(mean_loss)
+                if writer is not None:
+                    writer.add_scalars(step, [("loss", float(mean_loss) / world), ("learning_rate", tj["learning_rate"]),
+                                              ("batch_size", tj["batch_size"])] + scalars)
             if step % 50 == 0 or staged is None:
                 total, count = total + float(loss), count + 1
         if dist is not None:
@@ -339,6 +403,9 @@ def main(args):
             dist.barrier()                                               # nobody runs ahead of the checkpoint
         if validate and (epoch + 1) % args.validation_interval == 0:
             report_validation("epoch %d" % (epoch + 1))
+    for w in [writer] + list(eval_writers.values()):
+        if w is not None:
+            w.close()
     if dist is not None:
         dist.destroy_process_group()
 

@@ -424,6 +424,29 @@ int dd_loss_msssim_fwd(const dd_loss_msssim_desc* desc, int B, int H, int W, flo
 /* dpred += grad_scale * d term / d pred, routed through the combined product (d color += g (direct + indirect), d direct += g color,
  * d indirect += g color) and the image sum.  Same desc / scratch as the forward it follows on the same stream. */
 int dd_loss_msssim_bwd(const dd_loss_msssim_desc* desc, int B, int H, int W, float* scratch, float grad_scale, dd_stream stream);
+/* Tracked ms_ssim (track_ms_ssim of the statistics sections; add_tracked_metrics_to_dictionary Training.py:293-294 -> ms_ssim :178-204): the
+ * forward kernels of dd_loss_msssim_fwd on the same scratch layout, but instead of adding a weighted term to a loss they leave
+ *   ms_out[s * B + b] = MS of source s and image b (the mean over the 3 channels of the three-factor product)
+ * for the sources with a POSITIVE weight in desc (the weight only selects: its value is not used), listed as features in index order, then
+ * combined features, then the image.  The tracked scalar is 1 - mean over images of MS (Training.py:203).  dpred is not touched; the
+ * scratch must not be the one a pending dd_loss_msssim_bwd still reads.  No host sync. */
+int dd_loss_msssim_values(const dd_loss_msssim_desc* desc, int B, int H, int W, float* scratch, float* ms_out, dd_stream stream);
+
+/* ---- tracked metrics (statistics / statistics_masked of Training.json: BaseFeatureTraining.add_tracked_metrics_to_dictionary
+ * Training.py:283-302, add_tracked_summaries :246-265) of ONE scale.  Reads the sources of a dd_loss_desc -- pred / target, pred_ld /
+ * target_ld, nch (1 or 3), comb, image_combined / image_features, mask_feature / comb_mask_feature, kind, epsilon; weights, dpred, mask_sums
+ * and the pred_std fusion fields are ignored, pred[] must hold the final predictions -- and writes, for every source and EVERY IMAGE b,
+ *   table[(slot * B + b) * 4 + 0] = sum over the image's pixels of the channel-summed LossDifference            (difference, Training.py:116-129)
+ *   table[(slot * B + b) * 4 + 1] = sum over its H(W-1) horizontal and (H-1)W vertical pairs of the variation difference  (:139-176, :304-348)
+ *   table[(slot * B + b) * 4 + 2] = sum of difference * mask                                                    (:121-124, :131-137)
+ *   table[(slot * B + b) * 4 + 3] = sum of mask = non-zero mask of the target of mask_feature (0 when that is -1)   (:379-392, :434-437)
+ * slot = f for feature f, DD_MAX_FEATURES + k for combined feature k, DD_MAX_FEATURES + DD_MAX_COMBINED for the combined image; rows of
+ * sources the descriptor does not have are written as zeros.  table: DD_METRIC_SOURCES * B * 4 floats, 16-byte aligned, as is scratch
+ * (>= dd_loss_metrics_scratch_bytes).  Per-image rows let the host leave the repeated examples of a padded batch out.  All arithmetic fp32;
+ * every sum has a fixed order (no atomics): two runs give the same bits.  desc is a HOST struct (copied by value).  No host sync. */
+#define DD_METRIC_SOURCES (DD_MAX_FEATURES + DD_MAX_COMBINED + 1)
+long dd_loss_metrics_scratch_bytes(int B, int H, int W);
+int dd_loss_metrics(const dd_loss_desc* desc, int B, int H, int W, float* scratch, float* table, dd_stream stream);
 
 /* ---- Adam, TensorFlow formulation (tf.train.AdamOptimizer, Training.py:701-702), flat arenas */
 int dd_adam_step(float* params, const float* grads, float* m, float* v, long n, float lr_t, float beta1, float beta2,
