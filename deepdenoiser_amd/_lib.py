@@ -26,7 +26,7 @@ SYMBOLS = (
     "dd_kpcn_head_fwd", "dd_kpcn_head_bwd", "dd_kpcn_head_bwd_multi", "dd_assemble_input", "dd_assemble_input_frames", "dd_conv3x3_bwd", "dd_conv3x3_bwd_multi", "dd_convt2x2_fwd", "dd_convt2x2_bwd", "dd_conv3x3_ks",
     "dd_conv_pw_count", "dd_wgrad_pw_count", "dd_space_to_depth2", "dd_convt3_wgrad", "dd_compose_stream_plan", "dd_compose_bwd_scratch_bytes",
     "dd_loss_msssim_scratch_bytes", "dd_loss_msssim_fwd", "dd_loss_msssim_bwd", "dd_loss_msssim_values",
-    "dd_loss_metrics_scratch_bytes", "dd_loss_metrics",
+    "dd_loss_metrics_scratch_bytes", "dd_loss_metrics", "dd_loss_head_path_count",
 )
 
 
@@ -264,6 +264,8 @@ def load():
     lib.dd_invert_std_fwd.argtypes = [vp, vp, l, i, f, f, vp]
     lib.dd_invert_std_bwd.argtypes = [vp, vp, vp, l, i, f, f, vp]
     lib.dd_loss_head.argtypes = [C.POINTER(LossDesc), i, i, i, vp, f, vp]
+    lib.dd_loss_head_path_count.argtypes = [i]
+    lib.dd_loss_head_path_count.restype = C.c_long
     lib.dd_loss_msssim_scratch_bytes.argtypes = [i, i, i, i]
     lib.dd_loss_msssim_scratch_bytes.restype = C.c_long
     lib.dd_loss_msssim_fwd.argtypes = [C.POINTER(MsSsimDesc), i, i, i, vp, vp, vp]

@@ -34,6 +34,7 @@ __device__ __forceinline__ Val3 feature_value(const dd_loss_desc& d, int f, long
   return v;
 }
 __device__ __forceinline__ Val3 combined_value(const dd_loss_desc& d, int k, long i) {      // color * (direct + indirect)
+#pragma clang fp contract(off)      // one rounding per operation wherever a source value is formed (loss_head_kernel / loss_general_kernel)
   const Val3 c = feature_value(d, d.comb[k][0], i), dr = feature_value(d, d.comb[k][1], i), in = feature_value(d, d.comb[k][2], i);
   Val3 v;
 #pragma unroll
@@ -41,6 +42,7 @@ __device__ __forceinline__ Val3 combined_value(const dd_loss_desc& d, int k, lon
   return v;
 }
 __device__ __forceinline__ Val3 image_value(const dd_loss_desc& d, long i) {                 // sum of the combined features and single passes
+#pragma clang fp contract(off)
   Val3 v = {{0.f, 0.f, 0.f}, {0.f, 0.f, 0.f}};
   for (int j = 0; j < d.n_image_combined; ++j) {
     const Val3 a = combined_value(d, d.image_combined[j], i);

@@ -1299,6 +1299,7 @@ extern "C" int dd_invert_std_bwd(const float* x, const float* dy, float* dx, lon
 template <typename F>
 __device__ __forceinline__ void source_terms(F value, long i, int x, int y, int H, int W, int nch, float w_mean, float w_var, int kind,
                                              float eps, float grad_scale, float& loss, float (&g)[3]) {
+#pragma clang fp contract(off)
   g[0] = g[1] = g[2] = 0.f;
   if (w_mean == 0.f && w_var == 0.f) return;
   const Val3 c = value(i);
@@ -1332,6 +1333,7 @@ __device__ __forceinline__ void source_terms(F value, long i, int x, int y, int 
 
 // per-pixel weight of the masked mean: mask / mask_sum (0 when the batch has no masked pixel, Training.py:133-137)
 __device__ __forceinline__ float masked_pixel_weight(const dd_loss_desc& d, float w, int mask_f, int src, long i) {
+#pragma clang fp contract(off)
   if (w == 0.f || mask_f < 0 || d.mask_sums == nullptr) return 0.f;
   const float msum = d.mask_sums[src];
   return msum > 0.f ? w * target_mask(d, mask_f, i) / msum : 0.f;
@@ -1374,6 +1376,7 @@ extern "C" int dd_loss_mask_sums(const dd_loss_desc* desc, int B, int H, int W, 
 
 __global__ void loss_head_kernel(const dd_loss_desc d, long npix, int H, int W, float inv_count, float inv_count_var, float grad_scale,
                                  float* __restrict__ loss_out) {
+#pragma clang fp contract(off)      // (see loss_general_kernel: its dpred and loss_head_kernel's agree to the bit)
   __shared__ float red[256];
   float loss = 0.f;
   // grid-stride: a few thousand workgroups walk all pixels, so the descriptor (kernel argument, ~1 KB of scalar loads per wave) and the
@@ -1503,7 +1506,9 @@ __global__ __launch_bounds__(256) void loss_simple_kernel(const LossSimpleP P) {
 // ([feature][p0 p1 p2 t0 t1 t2 g0 g1 g2][lane]) -- every global value is read once (the loads of all features are in flight together) and every
 // gradient written once.  loss_head_kernel re-read a feature per term and accumulated the combined / image gradients with global read-modify-
 // writes: ~300 dependent memory operations per thread, 66 us even for the 8 192 pixels of the coarsest scale.  Same terms in the same order,
-// so dpred is bit-identical to loss_head_kernel's.  The inverse standardization fuses exactly as in loss_simple_kernel.
+// and -- with FMA contraction off in both kernels and in the helpers they share: hipcc fused different multiply-add pairs of the two, which
+// left their gradients 1 ulp apart -- dpred is bit-identical to loss_head_kernel's (tests/test_gpu_loss_ops.py).  The inverse standardization
+// fuses exactly as in loss_simple_kernel.
 __device__ __forceinline__ float invert_fwd(float x, float mean, float std, int log1p, float& dinv) {
   float z = x * std + mean;
   dinv = std;
@@ -1514,6 +1519,7 @@ __device__ __forceinline__ float invert_fwd(float x, float mean, float std, int 
   return z;
 }
 __global__ __launch_bounds__(64) void loss_general_kernel(const dd_loss_desc d, long npix, float inv_count, float grad_scale, float* __restrict__ loss_out) {
+#pragma clang fp contract(off)
   extern __shared__ float lg_sm[];                       // [n_features][9][64]
   const int lane = threadIdx.x;
   float loss = 0.f;
@@ -1522,6 +1528,7 @@ __global__ __launch_bounds__(64) void loss_general_kernel(const dd_loss_desc d, 
   auto G = [&](int f, int c) -> float& { return lg_sm[(f * 9 + 6 + c) * 64 + lane]; };
   // mean term of one source: adds to `loss`, returns dLoss/dvalue
   auto term = [&](const float (&p)[3], const float (&t)[3], int nch, float w, float (&g)[3]) {
+#pragma clang fp contract(off)
     g[0] = g[1] = g[2] = 0.f;
     if (w == 0.f) return;
     for (int ch = 0; ch < nch; ++ch) {
@@ -1532,6 +1539,7 @@ __global__ __launch_bounds__(64) void loss_general_kernel(const dd_loss_desc d, 
     }
   };
   auto masked_w = [&](float w, int mask_f, int src) -> float {      // masked_pixel_weight with the mask feature's target taken from LDS
+#pragma clang fp contract(off)
     if (w == 0.f || mask_f < 0 || d.mask_sums == nullptr) return 0.f;
     const float msum = d.mask_sums[src];
     float sa = 0.f;
@@ -1539,6 +1547,7 @@ __global__ __launch_bounds__(64) void loss_general_kernel(const dd_loss_desc d, 
     return msum > 0.f ? w * (sa > 0.f ? 1.f : 0.f) / msum : 0.f;
   };
   auto comb_val = [&](int k, float (&p)[3], float (&t)[3]) {
+#pragma clang fp contract(off)
     const int fc = d.comb[k][0], fd = d.comb[k][1], fi = d.comb[k][2];
 #pragma unroll
     for (int c = 0; c < 3; ++c) { p[c] = P(fc, c) * (P(fd, c) + P(fi, c)); t[c] = Tg(fc, c) * (Tg(fd, c) + Tg(fi, c)); }
@@ -1653,6 +1662,10 @@ __global__ __launch_bounds__(64) void loss_general_kernel(const dd_loss_desc d, 
   dd_det_end();
 }
 
+// launches so far of loss_simple_kernel (0), loss_general_kernel (1), loss_head_kernel (2): host-side, for tests (as dd_conv_pw_count)
+static long g_loss_path_launches[3] = {0, 0, 0};
+extern "C" long dd_loss_head_path_count(int path) { return path >= 0 && path < 3 ? g_loss_path_launches[path] : -1; }
+
 extern "C" int dd_loss_head(const dd_loss_desc* desc, int B, int H, int W, float* loss_out, float grad_scale, dd_stream stream) {
   DD_REQUIRE(desc && loss_out && desc->n_features > 0 && desc->n_features <= DD_MAX_FEATURES && desc->n_combined <= DD_MAX_COMBINED,
              "dd_loss_head: bad descriptor");
@@ -1697,6 +1710,7 @@ extern "C" int dd_loss_head(const dd_loss_desc* desc, int B, int H, int W, float
     const long cap = 1024L;      // (one atomic per workgroup into ONE address: 2 048 of them measured 8 us slower than 1 024 over the three scales)
     hipLaunchKernelGGL(loss_simple_kernel, dim3((unsigned)(want < cap ? (want < 1 ? 1 : want) : cap)), dim3(256), 0, S(stream), P);
     DD_LAUNCH_CHECK();
+    ++g_loss_path_launches[0];
     return DD_OK;
   }
   if (pixel_local && (general_on || fused_any)) {
@@ -1706,12 +1720,14 @@ extern "C" int dd_loss_head(const dd_loss_desc* desc, int B, int H, int W, float
     const long want = (npix + 63) / 64;
     hipLaunchKernelGGL(loss_general_kernel, dim3((unsigned)(want < 8192 ? want : 8192)), dim3(64), lds, S(stream), *desc, npix, 1.f / (float)npix, grad_scale, loss_out);
     DD_LAUNCH_CHECK();
+    ++g_loss_path_launches[1];
     return DD_OK;
   }
   dd_det_sync();
   hipLaunchKernelGGL(loss_head_kernel, dim3(min(grid_for(npix), 2048u)), dim3(256), 0, S(stream), *desc, npix, H, W, 1.f / (float)npix,
                      npairs > 0 ? 1.f / (float)npairs : 0.f, grad_scale, loss_out);
   DD_LAUNCH_CHECK();
+  ++g_loss_path_launches[2];
   return DD_OK;
 }
 

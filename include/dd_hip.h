@@ -346,7 +346,9 @@ typedef struct {
   int n_features;
   const float* pred[DD_MAX_FEATURES];    /* [B,H,W,pred_ld] internal prediction (1-channel passes use channel 0) */
   const float* target[DD_MAX_FEATURES];  /* [B,H,W,target_ld], first nch channels used */
-  float* dpred[DD_MAX_FEATURES];         /* [B,H,W,3] overwritten (all 3 channels) */
+  float* dpred[DD_MAX_FEATURES];         /* [B,H,W,3]; of a feature that carries a weight (its own, or through a combined / image term), or
+                                            pred_std: overwritten, all 3 channels.  Of a feature that carries NO weight: left untouched by the
+                                            flat-stream kernel and zeroed by the other two -- callers must not rely on either */
   int target_ld[DD_MAX_FEATURES];        /* pixel stride of target */
   int pred_ld[DD_MAX_FEATURES];          /* pixel stride of pred (3, or 4 when a source is echoed) */
   int nch[DD_MAX_FEATURES];
@@ -383,8 +385,13 @@ typedef struct {
 /* mask_sums[src] = sum over [B,H,W] of sign(sum_c |target_c|) of the source's mask feature, for every source with a masked weight
  * (features first, then combined at DD_MAX_FEATURES + k).  The masked mean divides by this BATCH-global count (Training.py:131-137). */
 int dd_loss_mask_sums(const dd_loss_desc* desc, int B, int H, int W, float* mask_sums, dd_stream stream);
-/* loss_out[0] += total weighted loss of this scale; dpred written. desc is a HOST struct (copied by value). */
+/* loss_out[0] += total weighted loss of this scale; dpred written (see dd_loss_desc.dpred for features without a weight). desc is a HOST
+ * struct (copied by value). */
 int dd_loss_head(const dd_loss_desc* desc, int B, int H, int W, float* loss_out, float grad_scale, dd_stream stream);
+/* dd_loss_head launches so far, per kernel: path 0 the flat-stream kernel (features-only descriptors), 1 the per-pixel kernel (no variation
+ * term), 2 the older kernel (everything else; DD_LOSS_SIMPLE=0 / DD_LOSS_GENERAL=0 send the first two here).  Host-side counter for tests, as
+ * dd_conv_pw_count; -1 for any other path. */
+long dd_loss_head_path_count(int path);
 
 /* ---- MS-SSIM loss term (BaseFeatureTraining.ms_ssim Training.py:178-204, added ONCE with ms_ssim_weight alone at Training.py:231-232: no
  * multi-scale scale factor, always on predicted[0] / target[0]; tf.image.ssim_multiscale with max_val 1 and the THREE power factors

@@ -50,6 +50,9 @@ def test_invalid_arguments_return_status_not_exception(lib):
     assert b"square" in lib.dd_last_error()
     assert lib.dd_augment(src, dst, 2, 1, 8, 8, draws, _lib.AUG_PLAIN, 0, 0, 0, 0, None) == -1
     assert lib.dd_loss_mask_sums(None, 1, 8, 8, None, None) == -1
+    # the launch counters of dd_loss_head's three kernels: host-side, -1 for a path that does not exist
+    assert [lib.dd_loss_head_path_count(p) >= 0 for p in range(3)] == [True] * 3
+    assert lib.dd_loss_head_path_count(-1) == -1 and lib.dd_loss_head_path_count(3) == -1
     assert lib.dd_maxpool_fwd(None, 8, None, 8, None, 8, 1, 8, 8, 3, 2, 1, _lib.DD_BF16, None) == -1
 
 

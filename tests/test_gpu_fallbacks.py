@@ -42,6 +42,11 @@ CASES = {   # name: (environment of the child, -k expression[, test file (defaul
                                        "test_small_networks_half_precision and (cfg2 or example_json or ragged)", "test_gpu_round3.py"),
     "tile_compose_kernels_bit_faithful": ({"DD_COMPOSE_STREAM": "0", "DD_COMPOSE_STREAM_BWD": "0"},
                                           "test_backward_of_the_fused_head_and_compose_kernels_is_bit_faithful", "test_gpu_round3.py"),
+    # the op-level loss cases (tests/test_gpu_loss_ops.py) with both newer loss kernels off: every non-fused descriptor runs on loss_head_kernel
+    # against the same float64 reference and gates (left out: the wrap sizes aimed at the two kernels that cannot run, and the test that needs
+    # the per-pixel kernel in its own process)
+    "loss_ops_on_the_older_kernel": ({"DD_LOSS_SIMPLE": "0", "DD_LOSS_GENERAL": "0"},
+                                     "not wrap_flat and not wrap_pixel and not bit_identical", "test_gpu_loss_ops.py"),
 }
 
 
