@@ -223,6 +223,26 @@ def convt3_s2d_blocks():
     return out
 
 
+class _Late:
+    """An entry of a launch list before Graph.finalize(): make() returns the bound launch, which takes the entry's place together with what
+    the builders hung on the entry (tag, grad_params, keep, origin, the merge descriptors)."""
+
+    def __init__(self, make, tag, **attrs):
+        self.make, self.tag = make, tag
+        self.origin = getattr(make, "__qualname__", "")      # which builder queued this launch (tools/step_breakdown.py)
+        vars(self).update(attrs)
+
+    def bind(self):
+        run = self.make()
+        if not hasattr(run, "info"):
+            run.info = None
+        vars(run).update({k: v for k, v in vars(self).items() if k != "make"})
+        return run
+
+    def __call__(self, stream):
+        raise RuntimeError("launch queued by %s is not bound: Graph.finalize() has not run" % self.origin)
+
+
 class Graph:
     def __init__(self, device, dtype="f32", params=None):
         assert dtype in _CODE
@@ -240,21 +260,22 @@ class Graph:
     def register_pack(self, kernel, buf, taps, n, k, n_pad, k_pad, st, sn, sk, flip, src_offset=0, dst_offset=0, dst_ld=0, dst_tap_stride=0):
         """dst_offset / dst_ld / dst_tap_stride (elements): this record fills the [n_pad][k_pad] corner at `dst_offset` of every tap of a wider
         image [taps][n_pad][dst_ld] (stacked reductions: the gather-form data gradient of a dense block)."""
+        assert not self.pack_ops or isinstance(self.pack_ops[0], _Late), "the pack table of a finalized graph is already on the device"
         self._pack_records.append((kernel, buf, taps, n, k, n_pad, k_pad, st, sn, sk, flip, src_offset, dst_offset, dst_ld, dst_tap_stride))
         if not self.pack_ops:
-            state = {}
+            self.pack_ops.append(self._defer(self._pack_call, "pack_weights"))
 
-            def pack_all(stream):
-                if state.get("n") != len(self._pack_records):   # (re)build the device table when layers were added
-                    tab = (L.PackDesc * len(self._pack_records))()
-                    for i, (kern, b, tp, nn, kk, npad, kpad, s_t, s_n, s_k, fl, off, doff, dld, dts) in enumerate(self._pack_records):
-                        tab[i] = L.PackDesc(self.params.value_ptr(kern) + 4 * off, b.data_ptr() + doff * _ESZ[self.dtype], tp, nn, kk, npad, kpad, fl,
-                                            s_t, s_n, s_k, dld, dts)
-                    state["dev"] = torch.frombuffer(bytearray(bytes(tab)), dtype=torch.uint8).to(self.device)
-                    state["n"] = len(self._pack_records)
-                L.check(self.lib.dd_pack_weights_batched(state["dev"].data_ptr(), state["n"], self.code, stream))
-            pack_all.tag = "pack_weights"
-            self.pack_ops.append(pack_all)
+    def _pack_call(self):
+        lib, code, n = self.lib, self.code, len(self._pack_records)
+        tab = (L.PackDesc * n)()
+        for i, (kern, b, tp, nn, kk, npad, kpad, s_t, s_n, s_k, fl, off, doff, dld, dts) in enumerate(self._pack_records):
+            tab[i] = L.PackDesc(self.params.value_ptr(kern) + 4 * off, b.data_ptr() + doff * _ESZ[self.dtype], tp, nn, kk, npad, kpad, fl,
+                                s_t, s_n, s_k, dld, dts)
+        dev = torch.frombuffer(bytearray(bytes(tab)), dtype=torch.uint8).to(self.device)
+
+        def pack_all(stream, dev=dev):
+            L.check(lib.dd_pack_weights_batched(dev.data_ptr(), n, code, stream))
+        return pack_all
 
     # ------------------------------------------------------------------ tensors
     def tensor(self, B, H, W, C, dtype=None, relu=False, requires_grad=True, ld=None, zero=True):
@@ -316,28 +337,17 @@ class Graph:
                 if len(chunk) < 2:
                     continue
                 members = [ops[i].weights_only for i in chunk]
-                records = []
-                for gy, x, layer in members:
-                    rec = {"flops": 2.0 * x.B * x.H * x.W * 9 * layer.cin * layer.cout, "B": x.B, "H": x.H, "W": x.W, "taps": 9, "m": layer.cin, "n": layer.cout}
-                    self.wgrad_records.append(rec)
-                    records.append(rec)
-                info = dict(records[0], flops=sum(r["flops"] for r in records), merged=len(members))
 
-                def run(stream, members=members, cell=[]):
-                    if not cell:      # parameter pointers exist only after ParamStore.finalize()
-                        arr = (L.ConvBwdArgs * len(members))()
-                        for a, (gy, x, layer) in zip(arr, members):
-                            a.dy, a.ld_dy, a.cout = gy.ptr, gy.ld, layer.cout
-                            a.x, a.ld_x, a.cin = x.ptr, x.ld, layer.cin
-                            a.wd, a.n_pad, a.k_pad, a.dx, a.ld_dx = None, 0, 0, None, 0
-                            a.dw, a.db = self.params.grad_ptr(layer.kernel), self.params.grad_ptr(layer.bias)
-                            a.B, a.H, a.W, a.use_mask, a.accumulate, a.dtype = x.B, x.H, x.W, 0, 0, self.code
-                        cell.append(arr)
-                    L.check(lib.dd_conv3x3_bwd_multi(cell[0], len(members), stream))
-                run.tag, run.info = "conv_wgrad", info
-                run.grad_params = tuple(p for _, _, layer in members for p in (layer.kernel, layer.bias))
-                run.keep = [(gy.buf, x.buf) for gy, x, _ in members]
-                put[chunk[-1]] = run
+                def make(members=members):
+                    arr = (L.ConvBwdArgs * len(members))()
+                    records = [self._conv_bwd_args(a, gy, x, layer, as_wgrad=True) for a, (gy, x, layer) in zip(arr, members)]
+
+                    def run(stream, arr=arr, n=len(members)):
+                        L.check(lib.dd_conv3x3_bwd_multi(arr, n, stream))
+                    run.info = dict(records[0], flops=sum(r["flops"] for r in records), merged=len(members))
+                    return run
+                put[chunk[-1]] = self._defer(make, "conv_wgrad", grad_params=tuple(p for _, _, layer in members for p in (layer.kernel, layer.bias)),
+                                             keep=[(gy.buf, x.buf) for gy, x, _ in members])
                 drop.update(chunk[:-1])
         if put:
             self.bwd_ops = [put.get(i, op) for i, op in enumerate(ops) if i not in drop]
@@ -393,28 +403,27 @@ class Graph:
         a.out, a.bias_out, a.bias_mode = None, None, 1
         a.B, a.H, a.W, a.taps, a.flags, a.dtype, a.ksplit = B, H, W, 9, flags, self.code, 0
         a.stack_blocks, a.stack_width, a.stack_m0 = nb, width, m0
+        for j, lay in enumerate(layers):
+            a.stack_out[j], a.stack_bias[j] = ps.grad_ptr(lay.kernel), ps.grad_ptr(lay.bias)
         lib = self.lib
         keep = (p.buf, q.buf)
 
-        def run(stream, a=a, keep=keep, bound=[]):
-            if not bound:      # parameter pointers exist only after ParamStore.finalize()
-                for j, lay in enumerate(layers):
-                    a.stack_out[j], a.stack_bias[j] = ps.grad_ptr(lay.kernel), ps.grad_ptr(lay.bias)
-                bound.append(1)
+        def run(stream, a=a, keep=keep):
             L.check(lib.dd_conv_wgrad(C.byref(a), stream))
-        run.info, run.tag = rec, "conv_wgrad"
+        run.info = rec
         return run
 
-    def _conv_bwd_call(self, gy, x, layer, wd, n_pad, k_pad, gx, use_mask, accumulate, as_wgrad=False):
-        """Data + weight + bias gradients of a 3x3 layer in one launch (csrc/dd_conv_bwd.hip); gx None: weight / bias gradients only
-        (as_wgrad: accounted with the weight-gradient launches)."""
+    def _conv_bwd_args(self, a, gy, x, layer, wd=None, n_pad=0, k_pad=0, gx=None, use_mask=False, accumulate=False, as_wgrad=False):
+        """Fills the dd_conv3x3_bwd arguments `a` of one layer and returns the launch's record (as_wgrad: accounted with the weight-gradient
+        launches)."""
         B, H, W = x.B, x.H, x.W
         if as_wgrad:
-            self.wgrad_records.append({"flops": 2.0 * B * H * W * 9 * layer.cin * layer.cout, "B": B, "H": H, "W": W, "taps": 9, "m": layer.cin, "n": layer.cout})
-        (self.bwd_records if not as_wgrad else []).append({"flops": (4.0 if gx is not None else 2.0) * B * H * W * 9 * layer.cin * layer.cout, "B": B, "H": H, "W": W, "taps": 9,
-                                 "n": layer.cin, "k": layer.cout, "accumulate": bool(accumulate), "weights_only": gx is None})
+            rec = {"flops": 2.0 * B * H * W * 9 * layer.cin * layer.cout, "B": B, "H": H, "W": W, "taps": 9, "m": layer.cin, "n": layer.cout}
+        else:
+            rec = {"flops": (4.0 if gx is not None else 2.0) * B * H * W * 9 * layer.cin * layer.cout, "B": B, "H": H, "W": W, "taps": 9,
+                   "n": layer.cin, "k": layer.cout, "accumulate": bool(accumulate), "weights_only": gx is None}
+        (self.wgrad_records if as_wgrad else self.bwd_records).append(rec)
         ps = self.params
-        a = L.ConvBwdArgs()
         a.dy, a.ld_dy, a.cout = gy.ptr, gy.ld, layer.cout
         a.x, a.ld_x, a.cin = x.ptr, x.ld, layer.cin
         a.wd, a.n_pad, a.k_pad = (wd.data_ptr() if wd is not None else None), n_pad, k_pad
@@ -422,12 +431,18 @@ class Graph:
         a.dw, a.db = ps.grad_ptr(layer.kernel), ps.grad_ptr(layer.bias)
         a.B, a.H, a.W = B, H, W
         a.use_mask, a.accumulate, a.dtype = int(bool(use_mask)), int(bool(accumulate)), self.code
+        return rec
+
+    def _conv_bwd_call(self, gy, x, layer, wd, n_pad, k_pad, gx, use_mask, accumulate, as_wgrad=False):
+        """Data + weight + bias gradients of a 3x3 layer in one launch (csrc/dd_conv_bwd.hip); gx None: weight / bias gradients only."""
+        a = L.ConvBwdArgs()
+        rec = self._conv_bwd_args(a, gy, x, layer, wd, n_pad, k_pad, gx, use_mask, accumulate, as_wgrad)
         lib = self.lib
         keep = (gy.buf, x.buf, wd, gx.buf if gx is not None else None)
 
         def run(stream, a=a, keep=keep):
             L.check(lib.dd_conv3x3_bwd(C.byref(a), stream))
-        run.info = self.wgrad_records[-1] if as_wgrad else self.bwd_records[-1]
+        run.info = rec
         return run
 
     def _convt_call(self, x, y, layer, w, n_pad, k_pad, relu, gx=None, use_mask=False, accumulate=False):
@@ -455,21 +470,27 @@ class Graph:
         run.info = self.convt_records[-1]
         return run
 
-    def _conv_ks_call(self, x, y, layer, wp, n_pad, k_pad, flags, mode=0):
-        """K-streamed 3x3 conv (csrc/dd_conv_ks.hip), one launch: mode 0 = the conv itself, 5 = the 3x3/s2 transposed conv as its four output
-        parities (the library runs channel blocks and parities as sub-problems of one grid)."""
+    def _conv_ks_call(self, name, x, y, n, k, wp, n_pad, k_pad, flags, mode=0, bias=None, mask=None, cin=None, extra_reads=0):
+        """K-streamed 3x3 conv (csrc/dd_conv_ks.hip) of n output from k input channels, one launch: mode 0 = the conv itself, 5 = the 3x3/s2
+        transposed conv as its four output parities (the library runs channel blocks and parities as sub-problems of one grid), 6 = its data
+        gradient (taps at offsets 0 / +1 over the `cin` stored channels of x).  bias: the layer whose bias is added; mask: the tensor whose sign
+        masks the output.  `name`: the launch's __name__ (tests tell the kernels apart by it)."""
         ps, lib = self.params, self.lib
+        rec = {"flops": 2.0 * x.B * x.H * x.W * 9 * k * n, "B": x.B, "H": x.H, "W": x.W, "taps": 9, "n": n, "k": k, "extra_reads": extra_reads, "flags": flags}
+        self.conv_records.append(rec)
         a = L.ConvKsArgs()
-        a.x, a.ldx, a.cin = x.ptr, x.ld, x.C
+        a.x, a.ldx, a.cin = x.ptr, x.ld, cin or k
         a.wp, a.n_pad, a.k_pad = wp.data_ptr(), n_pad, k_pad
-        a.bias, a.nbias = ps.value_ptr(layer.bias), layer.cout
+        a.bias, a.nbias = (ps.value_ptr(bias.bias), bias.cout) if bias is not None else (None, 0)
         a.y, a.ldy = y.ptr, y.ld
-        a.n0, a.n = 0, round_up(layer.cout, 4)
+        a.mask, a.ldmask = (mask.ptr, mask.ld) if mask is not None else (None, 0)
+        a.n0, a.n = 0, round_up(n, 4)
         a.B, a.H, a.W = x.B, x.H, x.W
         a.mode, a.flags, a.dtype = mode, flags, self.code
 
-        def run(stream, a=a, keep=(x.buf, y.buf, wp)):
+        def run(stream, a=a, keep=(x.buf, y.buf, wp, mask.buf if mask is not None else None)):
             L.check(lib.dd_conv3x3_ks(C.byref(a), stream))
+        run.__name__, run.info = name, rec
         return run
 
     def _bias_grad_call(self, gy, cout, bias_param):
@@ -514,16 +535,7 @@ class Graph:
             # Tiramisu's dense-block convs (pre-activation, reduction over the growing concat: K = 9 x up to 1 088 channels, 16 ... 128 new
             # channels): both operands streamed per 64-channel K-slice (csrc/dd_conv_ks.hip); the LDS-weight kernel can keep none of it resident
             wp, taps, n_pad, k_pad = layer.packed("fwd")
-            rec = {"flops": 2.0 * x.B * x.H * x.W * 9 * layer.cin * layer.cout, "B": x.B, "H": x.H, "W": x.W, "taps": 9, "n": layer.cout, "k": layer.cin,
-                   "extra_reads": 0, "flags": flags}
-            self.conv_records.append(rec)
-
-            def ks_fwd(stream, cell=[]):
-                if not cell:
-                    cell.append(self._conv_ks_call(x, y, layer, wp, n_pad, k_pad, flags))
-                cell[0](stream)
-            ks_fwd.tag, ks_fwd.info = "conv_igemm", rec
-            self.fwd(ks_fwd)
+            self.fwd(self._defer(lambda: self._conv_ks_call("ks_fwd", x, y, layer.cout, layer.cin, wp, n_pad, k_pad, flags, bias=layer), "conv_igemm"))
         else:
             wp, taps, n_pad, k_pad = layer.packed("fwd")
             self.fwd(self._defer(lambda: self._conv_call(x, wp, taps, n_pad, k_pad, ps.value_ptr(layer.bias), layer.cout, res, None, y,
@@ -561,9 +573,9 @@ class Graph:
                 # > 64 output channels: the weight-gradient role of the fused backward kernel per (input block, output block) pair of 64 x 64
                 # channels (dx = NULL).  Measured faster than the dedicated weight-gradient kernel: 96->96 at 64x64 154 -> 115 us,
                 # 128->128 at 32x32 71 -> 60 us against csrc/dd_conv_wgrad.hip
-                self.bwd(self._defer(lambda: self._conv_bwd_call(gy, x, layer, None, 0, 0, None, False, False, as_wgrad=True), "conv_wgrad"),
-                         grad_params=[layer.kernel, layer.bias])
-                self.bwd_ops[-1].weights_only = (gy, x, layer)      # (build_backward may run several of these as one launch: _merge_weights_only)
+                # (weights_only: build_backward may run several of these as one launch, _merge_weights_only)
+                self.bwd(self._defer(lambda: self._conv_bwd_call(gy, x, layer, None, 0, 0, None, False, False, as_wgrad=True), "conv_wgrad",
+                                     weights_only=(gy, x, layer)), grad_params=[layer.kernel, layer.bias])
             else:
                 self.bwd(self._defer(lambda: self._wgrad_call(x, layer.cin, gy, layer.cout, ps.grad_ptr(layer.kernel), x.B, x.H, x.W, taps, wflags,
                                                               ps.grad_ptr(layer.bias), 1), "conv_wgrad"), grad_params=[layer.kernel, layer.bias])
@@ -606,7 +618,7 @@ class Graph:
             self.conv(buf.view(0, cj), lay, relu=False, in_relu=True, out=buf.view(cj, f, relu=False), no_backward=gather)
         if not gather or not bool(getattr(self, "training", True)):      # the stacked images below only feed the backward
             return c0 + n * f
-        ps, lib, code = self.params, self.lib, self.code
+        ps = self.params
 
         def stacked_image(s0, sn, later):
             """MFMA operand [9][n_pad][k_pad]: row s - s0 (a channel of the target range), column block of conv i = its kernel W_i[8 - tap][s][:]."""
@@ -632,25 +644,10 @@ class Graph:
             def gather_call(s0, sn, first, img, n_pad, k_pad):
                 kch = (n - first) * f
                 x0 = c0 + first * f
-                rec = {"flops": 2.0 * buf.B * buf.H * buf.W * 9 * kch * sn, "B": buf.B, "H": buf.H, "W": buf.W, "taps": 9, "n": sn, "k": kch,
-                       "extra_reads": 2, "flags": L.ACCUM}
-                self.conv_records.append(rec)
                 # (thin target ranges stay on the K-streamed kernel: dd_conv_igemm's accumulate epilogue rounds the sum before it adds -- measured on the
                 #  prefix gradient 2.7e-3 against the 3e-4 of the single rounding this form exists for; it was 4 % faster on those launches)
-                a = L.ConvKsArgs()
-                a.x, a.ldx, a.cin = gbuf.ptr + x0 * _ESZ[self.dtype], gbuf.ld, kch
-                a.wp, a.n_pad, a.k_pad = img.data_ptr(), n_pad, k_pad
-                a.bias, a.nbias = None, 0
-                a.y, a.ldy = gbuf.ptr + s0 * _ESZ[self.dtype], gbuf.ld
-                a.mask, a.ldmask = buf.ptr + s0 * _ESZ[self.dtype], buf.ld
-                a.n0, a.n = 0, round_up(sn, 4)
-                a.B, a.H, a.W = buf.B, buf.H, buf.W
-                a.mode, a.flags, a.dtype = 0, L.ACCUM, code
-
-                def dense_gather(stream, a=a, keep=(gbuf.buf, buf.buf, img)):
-                    L.check(lib.dd_conv3x3_ks(C.byref(a), stream))
-                dense_gather.tag, dense_gather.info = "conv_igemm", rec
-                self.bwd(dense_gather)
+                self.bwd(self._defer(lambda: self._conv_ks_call("dense_gather", gbuf.view(x0, kch), gbuf.view(s0, sn), sn, kch, img, n_pad, k_pad, L.ACCUM,
+                                                                mask=buf.view(s0, sn), extra_reads=2), "conv_igemm"))
 
             # Round 5: the weight gradients of the block's convs are ONE launch behind the gathers (their output gradients are one contiguous
             # channel range, their inputs nested prefixes: dd_conv_wgrad's stacked form).  With 16 ... 32 new channels per conv a launch of its own
@@ -667,8 +664,8 @@ class Graph:
                 self.bwd(self._defer(lambda x=x, gy=gy, lay=lay: self._wgrad_call(x, lay.cin, gy, lay.cout, ps.grad_ptr(lay.kernel), x.B, x.H, x.W, 9, L.IN_RELU,
                                                                                    ps.grad_ptr(lay.bias), 1), "conv_wgrad"), grad_params=[lay.kernel, lay.bias])
             if stack:
-                self.bwd(self._wgrad_stack_call(buf.view(0, c0 + (n - 1) * f), gbuf.view(c0, n * f), layers, c0, f, buf.B, buf.H, buf.W, L.IN_RELU),
-                         "conv_wgrad", grad_params=[p_ for lay in layers for p_ in (lay.kernel, lay.bias)])
+                self.bwd(self._defer(lambda: self._wgrad_stack_call(buf.view(0, c0 + (n - 1) * f), gbuf.view(c0, n * f), layers, c0, f, buf.B, buf.H, buf.W,
+                                                                    L.IN_RELU), "conv_wgrad"), grad_params=[p_ for lay in layers for p_ in (lay.kernel, lay.bias)])
             if buf.requires_grad and c0 > 0:
                 gather_call(*plans[n - 1])
             buf.mark_grad_written()
@@ -773,16 +770,8 @@ class Graph:
                 L.check(lib.dd_zero_stuff(x.ptr, x.ld, z.ptr, z.ld, x.Cp, x.B, x.H, x.W, code, stream))
             self.fwd(stuff)
         if parity:
-            rec = {"flops": 2.0 * x.B * x.H * x.W * 9 * layer.cin * layer.cout, "B": x.B, "H": x.H, "W": x.W, "taps": 9, "n": layer.cout, "k": layer.cin,
-                   "extra_reads": 0, "flags": L.OUT_RELU if relu else 0}
-            self.conv_records.append(rec)
-
-            def ks_convt(stream, cell=[]):
-                if not cell:
-                    cell.append(self._conv_ks_call(x, y, layer, wp, n_pad, k_pad, L.OUT_RELU if relu else 0, mode=5))
-                cell[0](stream)
-            ks_convt.tag, ks_convt.info = "conv_igemm", rec
-            self.fwd(ks_convt)
+            self.fwd(self._defer(lambda: self._conv_ks_call("ks_convt", x, y, layer.cout, layer.cin, wp, n_pad, k_pad, L.OUT_RELU if relu else 0, mode=5,
+                                                            bias=layer), "conv_igemm"))
         else:
             self.fwd(self._defer(lambda: self._conv_call(z, wp, taps, n_pad, k_pad, ps.value_ptr(layer.bias), layer.cout, None, None, y,
                                                          z.B, z.H, z.W, L.OUT_RELU if relu else 0, nk=(layer.cout, layer.cin)), "conv_igemm"))
@@ -791,45 +780,32 @@ class Graph:
             gy = y.grad()
             self._self_mask(y, gy)
             sd = self.tensor(x.B, x.H, x.W, 4 * cp, requires_grad=False)      # the output gradient by output parity
-            es = _ESZ[self.dtype]
 
             def s2d(stream):
                 L.check(lib.dd_space_to_depth2(gy.ptr, gy.ld, sd.ptr, sd.ld, layer.cout, cp, x.B, x.H, x.W, code, stream))
             self.bwd(s2d)
             self.bwd(self._bias_grad_call(gy, layer.cout, layer.bias), grad_params=[layer.bias])
-            wrec = {"flops": 2.0 * x.B * x.H * x.W * 9 * layer.cin * layer.cout, "B": x.B, "H": x.H, "W": x.W, "taps": 9, "n": layer.cin, "k": layer.cout}
-            self.wgrad_records.append(wrec)
 
-            def convt3_wgrad(stream, cell=[]):
-                if not cell:      # (pointers into the parameter arena exist once the graph is finalised)
-                    wa = L.ConvT3WgradArgs()
-                    wa.s, wa.lds, wa.cout, wa.cp = sd.ptr, sd.ld, layer.cout, cp
-                    wa.x, wa.ldx, wa.cin = x.ptr, x.ld, layer.cin
-                    wa.dk = ps.grad_ptr(layer.kernel)
-                    wa.B, wa.H, wa.W, wa.dtype = x.B, x.H, x.W, code
-                    cell.append(wa)
-                L.check(lib.dd_convt3_wgrad(C.byref(cell[0]), stream))
-            convt3_wgrad.tag, convt3_wgrad.info = "conv_wgrad", wrec
-            self.bwd(convt3_wgrad, grad_params=[layer.kernel])
+            def make_wgrad():
+                wrec = {"flops": 2.0 * x.B * x.H * x.W * 9 * layer.cin * layer.cout, "B": x.B, "H": x.H, "W": x.W, "taps": 9, "n": layer.cin, "k": layer.cout}
+                self.wgrad_records.append(wrec)
+                wa = L.ConvT3WgradArgs()
+                wa.s, wa.lds, wa.cout, wa.cp = sd.ptr, sd.ld, layer.cout, cp
+                wa.x, wa.ldx, wa.cin = x.ptr, x.ld, layer.cin
+                wa.dk = ps.grad_ptr(layer.kernel)
+                wa.B, wa.H, wa.W, wa.dtype = x.B, x.H, x.W, code
+
+                def convt3_wgrad(stream, wa=wa, keep=(sd.buf, x.buf)):
+                    L.check(lib.dd_convt3_wgrad(C.byref(wa), stream))
+                convt3_wgrad.info = wrec
+                return convt3_wgrad
+            self.bwd(self._defer(make_wgrad, "conv_wgrad"), grad_params=[layer.kernel])
             if x.requires_grad:
                 gx = x.grad()
-                rec = {"flops": 2.0 * x.B * x.H * x.W * 9 * layer.cin * layer.cout, "B": x.B, "H": x.H, "W": x.W, "taps": 9, "n": layer.cin, "k": layer.cout,
-                       "extra_reads": (1 if x.relu else 0) + (1 if x.grad_written else 0), "flags": L.ACCUM if x.grad_written else 0}
-                self.conv_records.append(rec)
-                a = L.ConvKsArgs()
-                a.x, a.ldx, a.cin = sd.ptr, sd.ld, 4 * cp
-                a.wp, a.n_pad, a.k_pad = s2d_img.data_ptr(), s2d_n_pad, s2d_k_pad
-                a.bias, a.nbias = None, 0
-                a.y, a.ldy = gx.ptr, gx.ld
-                a.mask, a.ldmask = (x.ptr, x.ld) if x.relu else (None, 0)
-                a.n0, a.n = 0, round_up(layer.cin, 4)
-                a.B, a.H, a.W = x.B, x.H, x.W
-                a.mode, a.flags, a.dtype = 6, (L.ACCUM if x.grad_written else 0), code
-
-                def convt3_dgrad(stream, a=a, keep=(sd.buf, gx.buf, s2d_img)):
-                    L.check(lib.dd_conv3x3_ks(C.byref(a), stream))
-                convt3_dgrad.tag, convt3_dgrad.info = "conv_igemm", rec
-                self.bwd(convt3_dgrad)
+                masked, accumulate = x.relu, x.grad_written
+                self.bwd(self._defer(lambda: self._conv_ks_call("convt3_dgrad", sd, gx, layer.cin, layer.cout, s2d_img, s2d_n_pad, s2d_k_pad,
+                                                                L.ACCUM if accumulate else 0, mode=6, mask=x if masked else None, cin=4 * cp,
+                                                                extra_reads=int(bool(masked)) + int(bool(accumulate))), "conv_igemm"))
                 x.mark_grad_written()
 
         def backward():
@@ -890,22 +866,18 @@ class Graph:
 
     # ------------------------------------------------------------------ plumbing
     @staticmethod
-    def _defer(make, tag="pointwise"):
-        """Bind a launch lazily: parameter pointers exist only after ParamStore.finalize()."""
-        cell = []
-
-        def run(stream):
-            if not cell:
-                cell.append(make())
-                run.info = getattr(cell[0], "info", None)
-            cell[0](stream)
-        run.tag = tag
-        run.info = None
-        run.origin = getattr(make, "__qualname__", "")      # which builder queued this launch (tools/step_breakdown.py)
-        return run
+    def _defer(make, tag="pointwise", **attrs):
+        """Queue a launch whose arguments exist only once the graph is finalized (parameter pointers, device tables): make() -> the bound launch;
+        attrs: attributes of the launch (keep, ...)."""
+        return _Late(make, tag, **attrs)
 
     def finalize(self, seed=2):
+        """Allocates the parameters, then binds every queued launch, in program order.  From here on the three lists hold bound launches only:
+        calling one issues library calls and nothing else, and each carries its record (`info`) -- written to conv_records / wgrad_records /
+        bwd_records / convt_records by the bind, so a launch that was taken out of the lists before leaves no record."""
         self.params.finalize(self.device, seed)
+        for ops in (self.pack_ops, self.fwd_ops, self.bwd_ops):
+            ops[:] = [op.bind() if isinstance(op, _Late) else op for op in ops]
 
     @staticmethod
     def stream_ptr():
