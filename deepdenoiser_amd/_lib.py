@@ -27,6 +27,7 @@ SYMBOLS = (
     "dd_conv_pw_count", "dd_wgrad_pw_count", "dd_space_to_depth2", "dd_convt3_wgrad", "dd_compose_stream_plan", "dd_compose_bwd_scratch_bytes",
     "dd_loss_msssim_scratch_bytes", "dd_loss_msssim_fwd", "dd_loss_msssim_bwd", "dd_loss_msssim_values",
     "dd_loss_metrics_scratch_bytes", "dd_loss_metrics", "dd_loss_head_path_count",
+    "dd_loss_head_dscale", "dd_loss_msssim_bwd_dscale", "dd_grads_nonfinite", "dd_adam_step_scaled", "dd_scaler_update",
 )
 
 
@@ -138,6 +139,12 @@ class MsSsimDesc(C.Structure):      # dd_loss_msssim_desc
                 ("n_image_combined", C.c_int), ("image_combined", C.c_int * MAX_COMBINED),
                 ("n_image_features", C.c_int), ("image_features", C.c_int * MAX_FEATURES),
                 ("image_ssim_weight", C.c_float)]
+
+
+class ScalerState(C.Structure):
+    """dd_scaler_state (include/dd_hip.h): the device-resident record of the dynamic loss scale.  Five 4-byte words; `scale` is the first, so a
+    pointer to the record is a pointer to the scale (what the *_dscale loss launches take)."""
+    _fields_ = [("scale", C.c_float), ("good_steps", C.c_int), ("found_nonfinite", C.c_int), ("adam_t", C.c_int), ("skipped_total", C.c_int)]
 
 
 class AugmentDraw(C.Structure):
@@ -275,6 +282,11 @@ def load():
     lib.dd_loss_metrics_scratch_bytes.restype = C.c_long
     lib.dd_loss_metrics.argtypes = [C.POINTER(LossDesc), i, i, i, vp, vp, vp]
     lib.dd_adam_step.argtypes = [vp, vp, vp, vp, l, f, f, f, f, f, vp]
+    lib.dd_loss_head_dscale.argtypes = [C.POINTER(LossDesc), i, i, i, vp, vp, vp]
+    lib.dd_loss_msssim_bwd_dscale.argtypes = [C.POINTER(MsSsimDesc), i, i, i, vp, vp, vp]
+    lib.dd_grads_nonfinite.argtypes = [vp, l, vp, vp]
+    lib.dd_adam_step_scaled.argtypes = [vp, vp, vp, vp, l, C.c_double, C.c_double, C.c_double, f, f, vp, vp]
+    lib.dd_scaler_update.argtypes = [vp, f, f, i, f, f, vp]
     lib.dd_stitch.argtypes = [vp, i, i, vp, i, i, i, i, vp, i, vp]
     lib.dd_recombine.argtypes = [C.POINTER(RecombineDesc), l, vp]
     lib.dd_probe_tr16.argtypes = [vp, vp, vp, vp]

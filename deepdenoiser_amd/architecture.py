@@ -81,7 +81,10 @@ class Architecture:
         self.source_data_format, self.data_format = source_data_format, data_format
         assert dtype in ("f32", "bf16", "f16"), dtype
         self.device, self.dtype, self.seed = torch.device(device), dtype, seed
-        self.loss_scale = loss_scale          # None: the storage type's default (program.Program)
+        from . import loss_scale as LS
+        LS.parse(loss_scale, dtype)           # (refuses anything that is not None, a number, "dynamic" or a dict of dynamic settings)
+        self.loss_scale = loss_scale          # None: the storage type's default (program.Program); "dynamic" / a dict: loss_scale.py
+        self.loss_scaler = None               # the device-resident scaler of the dynamic mode, created with the first training program
         self.model_directory = parsed_json["model_directory"]
         self.number_of_sources_per_target = parsed_json["number_of_sources_per_target"]
         if self.number_of_sources_per_target != 1:

@@ -274,6 +274,15 @@ static inline void dd_det_sync() {
   armed |= 1ull << (dev & 63);
 }
 
+// ------------------------------------------------------------------------------------------------ loss-scale factor of a launch
+// The factor dL/dprediction is multiplied by: a value fixed when the launch is made, or -- dev != nullptr -- a word of device memory read
+// when the kernel RUNS (dynamic loss scaling: a captured hipGraph then picks the current scale up on every replay).  One uniform load per
+// wave; the multiply that follows is the same in both forms, so a by-value launch and a device launch of the same value agree to the bit.
+struct dd_grad_scale {
+  float value; const float* dev;
+  __device__ __forceinline__ float get() const { return dev ? *dev : value; }
+};
+
 // Host-side dispatch on the storage dtype: `T` is float / bf16_t / f16_t inside the statement.
 #define DD_DISPATCH_DTYPE(dtype, T, ...)                     \
   do {                                                       \

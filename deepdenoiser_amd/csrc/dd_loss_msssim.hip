@@ -261,7 +261,7 @@ __device__ __forceinline__ void route_comb(const MsArgs& a, int k, long pix, int
 }
 
 // sources [s_first, s_first + gridDim.z) -- at level 0 one launch per kind, so that no two workgroups of a launch add into the same dpred
-template <int K> __global__ __launch_bounds__(NTHREADS) void msssim_bwd_kernel(MsArgs a, int s_first, float grad_scale) {
+template <int K> __global__ __launch_bounds__(NTHREADS) void msssim_bwd_kernel(MsArgs a, int s_first, const dd_grad_scale grad_scale) {
   __shared__ float sx[BIN][BIN + 1], sy[BIN][BIN + 1];
   __shared__ float4 R[BIN][BP];          // row-pass maps; reused as the transposed row pass [BP][T]
   __shared__ float4 A[BP][BP + 1];       // (a, b, c) = coefficient * d value / d (mx, sxy, s2) at the valid positions
@@ -270,7 +270,7 @@ template <int K> __global__ __launch_bounds__(NTHREADS) void msssim_bwd_kernel(M
   const int ty = blockIdx.x / l.btx, tx = blockIdx.x % l.btx;
   const int b = blockIdx.y / 3, ch = blockIdx.y % 3, s = s_first + blockIdx.z;
   const int r0 = ty * T - HALO, c0 = tx * T - HALO;      // plane coordinates of local (0, 0)
-  const float coef = grad_scale * a.coef[(((long)s * a.B + b) * 3 + ch) * 4 + K];
+  const float coef = grad_scale.get() * a.coef[(((long)s * a.B + b) * 3 + ch) * 4 + K];
   for (int i = tid; i < BIN * BIN; i += NTHREADS) {
     int r = i / BIN, c = i % BIN;
     load_xy<K>(a, l, s, b, ch, r0 + r, c0 + c, sx[r][c], sy[r][c]);
@@ -480,11 +480,25 @@ template <int K> int launch_fwd(const MsArgs& a, hipStream_t st) {
   DD_LAUNCH_CHECK();
   return 0;
 }
-template <int K> int launch_bwd(const MsArgs& a, int s_first, int count, float grad_scale, hipStream_t st) {
+template <int K> int launch_bwd(const MsArgs& a, int s_first, int count, dd_grad_scale grad_scale, hipStream_t st) {
   if (count == 0) return 0;
   Level l = level_of(a.H, a.W, K);
   hipLaunchKernelGGL(msssim_bwd_kernel<K>, dim3(l.btx * l.bty, a.B * 3, count), dim3(NTHREADS), 0, st, a, s_first, grad_scale);
   DD_LAUNCH_CHECK();
+  return 0;
+}
+
+int bwd_launches(const dd_loss_msssim_desc* desc, int B, int H, int W, float* scratch, dd_grad_scale grad_scale, dd_stream stream) {
+  MsArgs a;
+  int kinds[3];
+  if (int e = make_args(desc, B, H, W, scratch, a, kinds)) return e;
+  hipStream_t st = (hipStream_t)stream;
+  if (int e = launch_bwd<2>(a, 0, a.n_src, grad_scale, st)) return e;
+  if (int e = launch_bwd<1>(a, 0, a.n_src, grad_scale, st)) return e;
+  // sources are listed by kind (features, combined, image): one launch per kind, in stream order
+  if (int e = launch_bwd<0>(a, 0, kinds[0], grad_scale, st)) return e;
+  if (int e = launch_bwd<0>(a, kinds[0], kinds[1], grad_scale, st)) return e;
+  if (int e = launch_bwd<0>(a, kinds[0] + kinds[1], kinds[2], grad_scale, st)) return e;
   return 0;
 }
 
@@ -532,15 +546,11 @@ extern "C" int dd_loss_msssim_values(const dd_loss_msssim_desc* desc, int B, int
 }
 
 extern "C" int dd_loss_msssim_bwd(const dd_loss_msssim_desc* desc, int B, int H, int W, float* scratch, float grad_scale, dd_stream stream) {
-  MsArgs a;
-  int kinds[3];
-  if (int e = make_args(desc, B, H, W, scratch, a, kinds)) return e;
-  hipStream_t st = (hipStream_t)stream;
-  if (int e = launch_bwd<2>(a, 0, a.n_src, grad_scale, st)) return e;
-  if (int e = launch_bwd<1>(a, 0, a.n_src, grad_scale, st)) return e;
-  // sources are listed by kind (features, combined, image): one launch per kind, in stream order
-  if (int e = launch_bwd<0>(a, 0, kinds[0], grad_scale, st)) return e;
-  if (int e = launch_bwd<0>(a, kinds[0], kinds[1], grad_scale, st)) return e;
-  if (int e = launch_bwd<0>(a, kinds[0] + kinds[1], kinds[2], grad_scale, st)) return e;
-  return 0;
+  return bwd_launches(desc, B, H, W, scratch, dd_grad_scale{grad_scale, nullptr}, stream);
+}
+// the same launches with the factor read from device memory when the kernels run (dynamic loss scaling, csrc/dd_loss_scale.hip)
+extern "C" int dd_loss_msssim_bwd_dscale(const dd_loss_msssim_desc* desc, int B, int H, int W, float* scratch, const float* grad_scale_dev,
+                                         dd_stream stream) {
+  DD_REQUIRE(grad_scale_dev != nullptr, "dd_loss_msssim_bwd_dscale: null grad_scale_dev");
+  return bwd_launches(desc, B, H, W, scratch, dd_grad_scale{1.f, grad_scale_dev}, stream);
 }

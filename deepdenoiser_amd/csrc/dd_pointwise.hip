@@ -1374,10 +1374,11 @@ extern "C" int dd_loss_mask_sums(const dd_loss_desc* desc, int B, int H, int W, 
   return DD_OK;
 }
 
-__global__ void loss_head_kernel(const dd_loss_desc d, long npix, int H, int W, float inv_count, float inv_count_var, float grad_scale,
+__global__ void loss_head_kernel(const dd_loss_desc d, long npix, int H, int W, float inv_count, float inv_count_var, const dd_grad_scale gsc,
                                  float* __restrict__ loss_out) {
 #pragma clang fp contract(off)      // (see loss_general_kernel: its dpred and loss_head_kernel's agree to the bit)
   __shared__ float red[256];
+  const float grad_scale = gsc.get();
   float loss = 0.f;
   // grid-stride: a few thousand workgroups walk all pixels, so the descriptor (kernel argument, ~1 KB of scalar loads per wave) and the
   // block reduction are paid once per ~8 pixels of a thread instead of once per pixel
@@ -1440,7 +1441,7 @@ struct LossSimpleF {
   const float* x; const float* t; float* p; float* d;
   float w; float mean, std; int log1p, one_channel, fused;
 };
-struct LossSimpleP { LossSimpleF f[DD_MAX_FEATURES]; int n; int kind; float eps, grad_scale; long nvec; float* loss_out; };
+struct LossSimpleP { LossSimpleF f[DD_MAX_FEATURES]; int n; int kind; float eps; dd_grad_scale grad_scale; long nvec; float* loss_out; };
 
 __device__ __forceinline__ void loss_simple_elem(const LossSimpleF& f, int kind, float eps, float gs, bool live, float x, float t, float& p, float& d, float& loss) {
   float dinv = 1.f;
@@ -1464,6 +1465,7 @@ __device__ __forceinline__ void loss_simple_elem(const LossSimpleF& f, int kind,
 __global__ __launch_bounds__(256) void loss_simple_kernel(const LossSimpleP P) {
   __shared__ float red[4];
   float loss = 0.f;
+  const float grad_scale = P.grad_scale.get();
   const long stride = (long)gridDim.x * 256;
   for (int fi = 0; fi < P.n; ++fi) {                      // block-uniform
     const LossSimpleF f = P.f[fi];
@@ -1484,7 +1486,7 @@ __global__ __launch_bounds__(256) void loss_simple_kernel(const LossSimpleP P) {
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
           const int c = c0 + k >= 3 ? (c0 + k >= 6 ? c0 + k - 6 : c0 + k - 3) : c0 + k;
-          loss_simple_elem(f, P.kind, P.eps, P.grad_scale, !f.one_channel || c == 0, xs[k], ts[k], ps[k], ds[k], loss);
+          loss_simple_elem(f, P.kind, P.eps, grad_scale, !f.one_channel || c == 0, xs[k], ts[k], ps[k], ds[k], loss);
         }
         if (f.fused) pv[v] = float4{ps[0], ps[1], ps[2], ps[3]};
         dv[v] = float4{ds[0], ds[1], ds[2], ds[3]};
@@ -1518,10 +1520,11 @@ __device__ __forceinline__ float invert_fwd(float x, float mean, float std, int 
   }
   return z;
 }
-__global__ __launch_bounds__(64) void loss_general_kernel(const dd_loss_desc d, long npix, float inv_count, float grad_scale, float* __restrict__ loss_out) {
+__global__ __launch_bounds__(64) void loss_general_kernel(const dd_loss_desc d, long npix, float inv_count, const dd_grad_scale gsc, float* __restrict__ loss_out) {
 #pragma clang fp contract(off)
   extern __shared__ float lg_sm[];                       // [n_features][9][64]
   const int lane = threadIdx.x;
+  const float grad_scale = gsc.get();
   float loss = 0.f;
   auto P = [&](int f, int c) -> float& { return lg_sm[(f * 9 + c) * 64 + lane]; };
   auto Tg = [&](int f, int c) -> float& { return lg_sm[(f * 9 + 3 + c) * 64 + lane]; };
@@ -1666,7 +1669,7 @@ __global__ __launch_bounds__(64) void loss_general_kernel(const dd_loss_desc d, 
 static long g_loss_path_launches[3] = {0, 0, 0};
 extern "C" long dd_loss_head_path_count(int path) { return path >= 0 && path < 3 ? g_loss_path_launches[path] : -1; }
 
-extern "C" int dd_loss_head(const dd_loss_desc* desc, int B, int H, int W, float* loss_out, float grad_scale, dd_stream stream) {
+static int loss_head_launch(const dd_loss_desc* desc, int B, int H, int W, float* loss_out, dd_grad_scale grad_scale, dd_stream stream) {
   DD_REQUIRE(desc && loss_out && desc->n_features > 0 && desc->n_features <= DD_MAX_FEATURES && desc->n_combined <= DD_MAX_COMBINED,
              "dd_loss_head: bad descriptor");
   DD_REQUIRE(desc->kind >= 1 && desc->kind <= 5, "dd_loss_head: unknown loss kind %d", desc->kind);
@@ -1729,6 +1732,14 @@ extern "C" int dd_loss_head(const dd_loss_desc* desc, int B, int H, int W, float
   DD_LAUNCH_CHECK();
   ++g_loss_path_launches[2];
   return DD_OK;
+}
+extern "C" int dd_loss_head(const dd_loss_desc* desc, int B, int H, int W, float* loss_out, float grad_scale, dd_stream stream) {
+  return loss_head_launch(desc, B, H, W, loss_out, dd_grad_scale{grad_scale, nullptr}, stream);
+}
+// the same launch with the factor read from device memory when the kernel runs (dynamic loss scaling, csrc/dd_loss_scale.hip)
+extern "C" int dd_loss_head_dscale(const dd_loss_desc* desc, int B, int H, int W, float* loss_out, const float* grad_scale_dev, dd_stream stream) {
+  DD_REQUIRE(grad_scale_dev != nullptr, "dd_loss_head_dscale: null grad_scale_dev");
+  return loss_head_launch(desc, B, H, W, loss_out, dd_grad_scale{1.f, grad_scale_dev}, stream);
 }
 
 // ------------------------------------------------------------------------------------------------ Adam (TF form)

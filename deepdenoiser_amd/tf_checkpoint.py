@@ -274,6 +274,12 @@ def _update_state(model_directory, name):
 
 
 # ---------------------------------------------------------------------------------------------------- the parameter arena
+# The two extra tensors of a model trained with a dynamic loss scale (loss_scale.py): the scale (float32) and the counters
+# [good_steps, adam_t, skipped_total] (int32).  adam_t is stored because skipped steps make it differ from global_step, which is what
+# _adam_step_from_powers falls back on once beta1_power has underflowed.  TensorFlow ignores variables a graph does not have.
+SCALE_KEY, STEPS_KEY = "dd_loss_scale/scale", "dd_loss_scale/steps"
+
+
 def _adam_step_from_powers(ck, beta1, beta2, global_step):
     """Number of Adam updates t behind a checkpoint.  TF stores beta1_power = beta1 ** (t + 1) and beta2_power = beta2 ** (t + 1)
     (float32): beta1_power resolves t exactly while it is a normal number (t < ~800 for 0.9), beta2_power up to ~8e4 steps;
@@ -334,6 +340,18 @@ def load_variables(arch, prefix, load_optimizer=True, strict=True, beta1=0.9, be
             used.add("beta2_power")
             info["adam_step"] = _adam_step_from_powers(ck, beta1, beta2, info["global_step"])
             arch.adam_step = info["adam_step"]
+    scaler = getattr(arch, "loss_scaler", None)
+    if scaler is not None:      # dynamic loss scale: the device record follows the checkpoint (its two tensors are `unused` to a static model)
+        state = {}
+        if load_optimizer and SCALE_KEY in ck and STEPS_KEY in ck:
+            good, adam_t, skipped = (int(x) for x in ck[STEPS_KEY].reshape(-1)[:3])
+            state.update(scale=float(ck[SCALE_KEY].reshape(-1)[0]), good_steps=good, adam_t=adam_t, skipped_total=skipped, found_nonfinite=0)
+            used.update((SCALE_KEY, STEPS_KEY))
+            if have_slots:
+                info["adam_step"] = arch.adam_step = adam_t
+        elif info["adam_step"] is not None:      # a checkpoint of a static run: the device counter starts from its Adam step
+            state["adam_t"] = info["adam_step"]
+        scaler.set_state(state)
     info["unused"] = [k for k in ck if k not in used and k != "global_step"]
     return info
 
@@ -355,6 +373,12 @@ def save_variables(arch, model_directory, global_step, save_optimizer=True, beta
     if save_optimizer:
         # tf.train.AdamOptimizer creates beta{1,2}_power with initial value beta and multiplies by beta in _finish(): after t
         # updates the variables hold beta ** (t + 1) (a fresh model saves beta, never 1.0 -- TF computes 1 - beta1_power)
+        scaler = getattr(arch, "loss_scaler", None)
+        if scaler is not None:      # dynamic loss scale: the count of APPLIED steps and the scale live on the device
+            state = scaler.state()
+            arch.adam_step = state["adam_t"]
+            tensors[SCALE_KEY] = np.array(state["scale"], dtype=np.float32)
+            tensors[STEPS_KEY] = np.array([state["good_steps"], state["adam_t"], state["skipped_total"]], dtype=np.int32)
         t = getattr(arch, "adam_step", 0)
         tensors["beta1_power"] = np.array(beta1 ** (t + 1), dtype=np.float32)
         tensors["beta2_power"] = np.array(beta2 ** (t + 1), dtype=np.float32)

@@ -26,7 +26,7 @@ import time
 import numpy as np
 import torch
 
-from . import summaries, tf_checkpoint, tfrecords
+from . import loss_scale, summaries, tf_checkpoint, tfrecords
 from .architecture import Architecture
 from .data_augmentation import DataAugmentation, DataAugmentationUsage
 from .metrics import MeanAccumulator
@@ -47,6 +47,9 @@ def parser():
     p.add_argument("--dtype", default="bf16", choices=["bf16", "f16", "f32"], help="storage type of activations (accumulation is fp32)")
     p.add_argument("--summary_steps", type=int, default=100,
                    help="Write the loss and the tracked metrics of the current mini-batch as TensorBoard scalars every this many steps (0: never).")
+    p.add_argument("--loss_scale", type=loss_scale.cli_value, default=None, metavar="{dynamic,<number>}",
+                   help="Loss scale of the optimisation step: 'dynamic' keeps it on the device (halved on an inf / NaN gradient, whose step is skipped, "
+                        "doubled after 2000 applied steps), a positive number fixes it.  Default: 4096 for f16, 1 for bf16 / f32.")
     p.add_argument("--seed", type=int, default=0, help="seed of the file / example shuffles and of the source index tuples (shared by all ranks)")
     return p
 
@@ -297,7 +300,8 @@ def main(args):
     tj = json.load(open(args.json_filename, encoding="utf-8"))
     directory = os.path.dirname(os.path.abspath(args.json_filename))
     aj = json.load(open(os.path.join(directory, tj["architecture"])))
-    arch = Architecture(aj, source_data_format="channels_last", data_format=args.data_format, device="cuda:%d" % local, dtype=args.dtype)
+    arch = Architecture(aj, source_data_format="channels_last", data_format=args.data_format, device="cuda:%d" % local, dtype=args.dtype,
+                        loss_scale=args.loss_scale)
     base = tj["base_tfrecords_directory"] if os.path.isabs(tj["base_tfrecords_directory"]) else os.path.join(directory, tj["base_tfrecords_directory"])
     if "training" not in tj["modes"]:
         raise Exception("No training mode found.")
@@ -387,6 +391,9 @@ def main(args):
                 mean_loss = loss.double().sum()
                 if dist is not None:
                     dist.all_reduce(mean_loss)
+                scaler = trainer.program.sync_adam_step()                # (the loss is about to be read back: the wait is paid for anyway)
+                if scaler is not None:
+                    scalars = [("loss_scale", scaler["scale"]), ("skipped_steps", scaler["skipped_total"])] + scalars
                 if writer is not None:
                     writer.add_scalars(step, [("loss", float(mean_loss) / world), ("learning_rate", tj["learning_rate"]),
                                               ("batch_size", tj["batch_size"])] + scalars)
@@ -396,8 +403,10 @@ def main(args):
             dist.barrier()
         if rank == 0:
             dt = max(time.time() - t0, 1e-9)
-            print("epoch %d: global_step %d, loss %.5f (%d steps, %.1f tiles/s, %d examples decoded)" % (
-                epoch + 1, step, total / max(count, 1), step - steps0, (step - steps0) * B * world / dt, stream.decoded))
+            skipped = (trainer.program.sync_adam_step() or {}).get("skipped_total", 0)
+            print("epoch %d: global_step %d, loss %.5f (%d steps, %.1f tiles/s, %d examples decoded)%s" % (
+                epoch + 1, step, total / max(count, 1), step - steps0, (step - steps0) * B * world / dt, stream.decoded,
+                ", %d steps skipped so far (loss scale)" % skipped if skipped else ""))
             tf_checkpoint.save_variables(arch, model_dir, global_step=step)
         if dist is not None:
             dist.barrier()                                               # nobody runs ahead of the checkpoint

@@ -157,6 +157,9 @@ class Trainer:
                 self._run_segment_eager(idx)
             self.reducer.launch(*sl)          # RCCL all-reduce of the slice that just became final (no-op for world 1)
         self.reducer.wait()
+        # Dynamic loss scale (loss_scale.py): the non-finite scan of adam() reads the WHOLE arena after the all-reduce.  A sum over the ranks
+        # that has an inf / NaN term is itself inf / NaN, so every rank sees the overflow of any rank in the same data and takes the same
+        # decision (skip and back off, or apply) without a collective of its own.
         prog.adam(grad_scale=self.reducer.grad_scale)
         return prog.loss_buf
 

@@ -388,6 +388,10 @@ int dd_loss_mask_sums(const dd_loss_desc* desc, int B, int H, int W, float* mask
 /* loss_out[0] += total weighted loss of this scale; dpred written (see dd_loss_desc.dpred for features without a weight). desc is a HOST
  * struct (copied by value). */
 int dd_loss_head(const dd_loss_desc* desc, int B, int H, int W, float* loss_out, float grad_scale, dd_stream stream);
+/* dd_loss_head with the factor of dL/dprediction read from device memory when the kernel RUNS (*grad_scale_dev, in practice the `scale` word of
+ * a dd_scaler_state): a captured hipGraph picks the current loss scale up on every replay.  Same kernels and the same multiply as the
+ * by-value entry: dpred is bit-identical to dd_loss_head(..., the value at *grad_scale_dev, ...).  No host sync. */
+int dd_loss_head_dscale(const dd_loss_desc* desc, int B, int H, int W, float* loss_out, const float* grad_scale_dev, dd_stream stream);
 /* dd_loss_head launches so far, per kernel: path 0 the flat-stream kernel (features-only descriptors), 1 the per-pixel kernel (no variation
  * term), 2 the older kernel (everything else; DD_LOSS_SIMPLE=0 / DD_LOSS_GENERAL=0 send the first two here).  Host-side counter for tests, as
  * dd_conv_pw_count; -1 for any other path. */
@@ -431,6 +435,8 @@ int dd_loss_msssim_fwd(const dd_loss_msssim_desc* desc, int B, int H, int W, flo
 /* dpred += grad_scale * d term / d pred, routed through the combined product (d color += g (direct + indirect), d direct += g color,
  * d indirect += g color) and the image sum.  Same desc / scratch as the forward it follows on the same stream. */
 int dd_loss_msssim_bwd(const dd_loss_msssim_desc* desc, int B, int H, int W, float* scratch, float grad_scale, dd_stream stream);
+/* dd_loss_msssim_bwd with grad_scale read from device memory when the kernels run (see dd_loss_head_dscale); bit-identical to the by-value entry. */
+int dd_loss_msssim_bwd_dscale(const dd_loss_msssim_desc* desc, int B, int H, int W, float* scratch, const float* grad_scale_dev, dd_stream stream);
 /* Tracked ms_ssim (track_ms_ssim of the statistics sections; add_tracked_metrics_to_dictionary Training.py:293-294 -> ms_ssim :178-204): the
  * forward kernels of dd_loss_msssim_fwd on the same scratch layout, but instead of adding a weighted term to a loss they leave
  *   ms_out[s * B + b] = MS of source s and image b (the mean over the 3 channels of the three-factor product)
@@ -458,6 +464,31 @@ int dd_loss_metrics(const dd_loss_desc* desc, int B, int H, int W, float* scratc
 /* ---- Adam, TensorFlow formulation (tf.train.AdamOptimizer, Training.py:701-702), flat arenas */
 int dd_adam_step(float* params, const float* grads, float* m, float* v, long n, float lr_t, float beta1, float beta2,
                  float eps, float grad_scale, dd_stream stream);
+
+/* ---- dynamic loss scaling on the device (csrc/dd_loss_scale.hip).  One record of DEVICE memory per optimizer: the loss launches multiply
+ * dL/dprediction by `scale` (dd_loss_head_dscale / dd_loss_msssim_bwd_dscale take &st->scale), and a step is
+ *   dd_grads_nonfinite -> dd_adam_step_scaled -> dd_scaler_update
+ * on one stream: the decision to skip an overflowed step, the scale and the Adam step counter never visit the host.  The host initialises the
+ * record (scale > 0, the rest 0, or the values of a checkpoint) and may read it back whenever it is willing to wait. */
+typedef struct {
+  float scale;            /* current loss scale */
+  int good_steps;         /* applied steps since the scale last changed */
+  int found_nonfinite;    /* set by dd_grads_nonfinite, cleared by dd_scaler_update */
+  int adam_t;             /* applied optimizer steps: the t of lr_t; skipped steps do not count */
+  int skipped_total;      /* steps skipped because a gradient was inf / NaN */
+} dd_scaler_state;
+/* st->found_nonfinite |= (any of grads[0 .. n) is inf or NaN); a flag that is set stays set.  grads 16-byte aligned.  One read of the arena, no
+ * write at all when every value is finite. */
+int dd_grads_nonfinite(const float* grads, long n, dd_scaler_state* st, dd_stream stream);
+/* dd_adam_step behind the device-side decision: writes NOTHING when st->found_nonfinite is set; otherwise the gradient is
+ * grads * grad_scale / st->scale and lr_t = lr * sqrt(1 - beta2^t) / (1 - beta1^t) with t = st->adam_t + 1, derived on the device in double
+ * (hence lr and the betas as doubles: the value the host formula of dd_adam_step's callers would give). */
+int dd_adam_step_scaled(float* params, const float* grads, float* m, float* v, long n, double lr, double beta1, double beta2,
+                        float eps, float grad_scale, const dd_scaler_state* st, dd_stream stream);
+/* after dd_adam_step_scaled, one thread.  Flag set: scale = max(scale * backoff, min_scale), good_steps = 0, ++skipped_total.  Flag clear:
+ * ++adam_t, ++good_steps, and when good_steps == growth_interval: scale = min(scale * growth, max_scale), good_steps = 0.  The flag is
+ * cleared.  Conventional values: growth 2, backoff 0.5, growth_interval 2000, min_scale 1, max_scale 2^24. */
+int dd_scaler_update(dd_scaler_state* st, float growth, float backoff, int growth_interval, float min_scale, float max_scale, dd_stream stream);
 
 /* ---- inference stitch (Prediction.py:384-441): copy crop windows of row-major tiles into the frame */
 typedef struct { int tile; int crop_y0, crop_y1, crop_x0, crop_x1; int dst_img, dst_y, dst_x; } dd_stitch_entry;
