@@ -14,6 +14,20 @@ DD_F32, DD_BF16, DD_F16 = 0, 1, 2
 IN_RELU, OUT_RELU, ACCUM, PIXSHUF, GATHER2X2 = 1, 2, 4, 8, 16
 MAX_FEATURES, MAX_COMBINED = 32, 8
 METRIC_SOURCES = MAX_FEATURES + MAX_COMBINED + 1      # DD_METRIC_SOURCES: rows of the dd_loss_metrics table per image
+# histogram records (dd_histogram_values / dd_loss_histograms): uint32 counts[nb] | double min, max, sum, sum_squares | uint64 num, nonfinite
+HISTOGRAM_DIFFERENCE, HISTOGRAM_VARIATION_DIFFERENCE, HISTOGRAM_MASKED_DIFFERENCE = 0, 1, 2
+HISTOGRAM_VALUES_SCRATCH_BYTES = 20480
+
+
+def histogram_stats_offset(nb):
+    """DD_HISTOGRAM_STATS_OFFSET"""
+    return (nb + 1) // 2 * 8
+
+
+def histogram_record_bytes(nb):
+    """DD_HISTOGRAM_RECORD_BYTES"""
+    return histogram_stats_offset(nb) + 48
+
 
 # every symbol include/dd_hip.h declares (checked by tests/test_abi.py)
 SYMBOLS = (
@@ -28,6 +42,7 @@ SYMBOLS = (
     "dd_loss_msssim_scratch_bytes", "dd_loss_msssim_fwd", "dd_loss_msssim_bwd", "dd_loss_msssim_values",
     "dd_loss_metrics_scratch_bytes", "dd_loss_metrics", "dd_loss_head_path_count",
     "dd_loss_head_dscale", "dd_loss_msssim_bwd_dscale", "dd_grads_nonfinite", "dd_adam_step_scaled", "dd_scaler_update",
+    "dd_histogram_values", "dd_loss_histograms_scratch_bytes", "dd_loss_histograms",
 )
 
 
@@ -281,6 +296,10 @@ def load():
     lib.dd_loss_metrics_scratch_bytes.argtypes = [i, i, i]
     lib.dd_loss_metrics_scratch_bytes.restype = C.c_long
     lib.dd_loss_metrics.argtypes = [C.POINTER(LossDesc), i, i, i, vp, vp, vp]
+    lib.dd_histogram_values.argtypes = [vp, l, vp, i, vp, vp, vp]
+    lib.dd_loss_histograms_scratch_bytes.argtypes = [i, i, i, i]
+    lib.dd_loss_histograms_scratch_bytes.restype = C.c_long
+    lib.dd_loss_histograms.argtypes = [C.POINTER(LossDesc), i, i, i, C.POINTER(C.c_int), i, vp, i, vp, vp, vp]
     lib.dd_adam_step.argtypes = [vp, vp, vp, vp, l, f, f, f, f, f, vp]
     lib.dd_loss_head_dscale.argtypes = [C.POINTER(LossDesc), i, i, i, vp, vp, vp]
     lib.dd_loss_msssim_bwd_dscale.argtypes = [C.POINTER(MsSsimDesc), i, i, i, vp, vp, vp]

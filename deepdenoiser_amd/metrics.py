@@ -6,7 +6,13 @@ Training.py:283-302, 704-719, 874-877).  This module holds the host side: which 
 and under its names (metric_plan), how the per-image sums of dd_loss_metrics / dd_loss_msssim_values (include/dd_hip.h) become their values
 (metric_values), and the running mean over batches (MeanAccumulator).  The launches are Program.metrics() (program.py).
 
-Not built: the four *_histogram flags (said once on stdout, then ignored).
+Histograms (the four *_histogram flags; BaseFeatureTraining.add_tracked_histograms, Training.py:267-281, written in TRAIN mode only, :679-686):
+histogram_plan lists the tags in the reference's call order, histogram_limits is TensorFlow's default bucket table, decode_histogram_records /
+histogram_values turn the device records of dd_histogram_values / dd_loss_histograms (include/dd_hip.h) into what a HistogramProto holds
+(Histogram::EncodeToProto with the empty buckets collapsed), merge_histogram_tables adds the tables of several ranks.  The TensorFlow side is
+restated from tensorflow/core/lib/histogram/histogram.cc (PARITY UNPINNED, like ssim_multiscale and the event format).  The launches are
+Program.histograms(); `python -m deepdenoiser_amd.train --histograms` writes them.  metric_plan alone still says once that the flags are set
+and nothing is written, unless its caller passes histograms=True.
 """
 import collections
 
@@ -73,7 +79,22 @@ def _check_masked(level, flags):
         raise NotImplementedError("%strack_ms_ssim: Not implemented (BaseFeatureTraining.masked_ms_ssim raises the same, Training.py:206-207)" % key)
 
 
-def metric_plan(arch, training_json, out=print):
+def _levels(arch, tj):
+    """(statistics flags, statistics_masked flags) of the three levels and the loaded target passes, after the checks metric_plan and
+    histogram_plan share: Alpha with any masked flag, statistics_masked.track_variation, statistics_masked.track_ms_ssim."""
+    fs, cf, ci = (tj[k] for k in _LEVELS)
+    stat = [_flags(lv.get("statistics")) for lv in (fs, cf, ci)]
+    masked = [_flags(lv.get("statistics_masked")) for lv in (fs, cf, ci)]
+    loaded = [f for f in arch.feature_predictions if f.is_target and f.load_data]
+    if any(masked[0].values()) and any(f.name == "Alpha" for f in loaded):      # Training.py:103-113
+        raise Exception("Masking is not supported for the alpha pass, because it does not seem to make sense. "
+                        "(features_training_settings.statistics_masked)")
+    for level, m in zip(_LEVELS, masked):
+        _check_masked(level, m)
+    return stat, masked, loaded
+
+
+def metric_plan(arch, training_json, out=print, histograms=False):
     """The ordered list of MetricEntry that the reference's add_tracked_metrics_to_dictionary calls produce for `arch` (an Architecture; no
     device is touched) and a parsed Training.json: the feature trainings in Training.main's order (target passes; a generated pass, load_data
     false, tracks nothing: Training.py:1020-1044), the combined feature trainings, the combined image training.  Per source: mean and
@@ -84,20 +105,13 @@ def metric_plan(arch, training_json, out=print):
 
     Raises, naming the key, when a flag that cannot be served is true: statistics_masked.track_variation, statistics_masked.track_ms_ssim,
     any masked tracking with an Alpha pass, track_ms_ssim of the features level with a loaded 1-channel pass (Program._check_ms_ssim adds
-    the tile-size rule when the launches are built).  A *_histogram flag is reported once through `out` and ignored."""
+    the tile-size rule when the launches are built).  A *_histogram flag is not this plan's business (histogram_plan): a caller that does
+    not write histograms (histograms=False) has that said once through `out`."""
     tj = training_json
-    fs, cf, ci = (tj[k] for k in _LEVELS)
-    stat = [_flags(lv.get("statistics")) for lv in (fs, cf, ci)]
-    masked = [_flags(lv.get("statistics_masked")) for lv in (fs, cf, ci)]
-    if any(s[h] for s in stat + masked for h in _HISTOGRAMS) and not _said_histograms:
+    stat, masked, loaded = _levels(arch, tj)
+    if not histograms and any(s[h] for s in stat + masked for h in _HISTOGRAMS) and not _said_histograms:
         _said_histograms.append(True)
         out("tracked metrics: the *_histogram flags of Training.json are set, but histograms are not written")
-    loaded = [f for f in arch.feature_predictions if f.is_target and f.load_data]
-    if any(masked[0].values()) and any(f.name == "Alpha" for f in loaded):      # Training.py:103-113
-        raise Exception("Masking is not supported for the alpha pass, because it does not seem to make sense. "
-                        "(features_training_settings.statistics_masked)")
-    for level, m in zip(_LEVELS, masked):
-        _check_masked(level, m)
     if stat[0]["track_ms_ssim"]:
         for f in loaded:
             if f.number_of_channels != 3:
@@ -159,6 +173,139 @@ def metric_values(plan, slot_of, tables, dims, real=None, ms_values=None, count=
         else:
             out.append(float(s[2] / s[3]) if s[3] > 0 else 0.0)
     return out
+
+
+# ---------------------------------------------------------------------------------------------------------------- histograms
+HistogramEntry = collections.namedtuple("HistogramEntry", "tag source kind scale_index")
+# kind: "difference" | "variation_difference" | "masked_difference" (DD_HISTOGRAM_* of include/dd_hip.h, in this order)
+HISTOGRAM_KINDS = ("difference", "variation_difference", "masked_difference")
+_STAT_KEYS = ("min", "max", "sum", "sum_squares")
+_said_nonfinite = set()
+
+
+def histogram_limits():
+    """TensorFlow's default bucket limits (InitDefaultBucketsInner, histogram.cc): v = 1e-12, while v < 1e20: append v, v *= 1.1 (IEEE double);
+    then DBL_MAX; the list is the negated list reversed, 0.0, the list.  1551 float64 values, [775] == 0.0."""
+    pos, v = [], 1e-12
+    while v < 1e20:
+        pos.append(v)
+        v *= 1.1
+    pos.append(np.finfo(np.float64).max)
+    return np.array([-x for x in reversed(pos)] + [0.0] + pos, dtype=np.float64)
+
+
+def histogram_plan(arch, training_json):
+    """The ordered list of HistogramEntry that the reference's add_tracked_histograms calls produce (Training.py:267-281, 679-686): sources in
+    Training.main's order; per source and scale (scale 0 only unless use_multiscale_metrics) the difference, the variation difference, then
+    the masked difference.  The rules of metric_plan hold: generated passes track nothing, a masked flag on a pass without a colour pass is
+    left out, Alpha with any masked flag raises, the combined levels exist only when combined_levels() says so.
+
+    statistics_masked.track_variation_difference_histogram raises, naming the key: like statistics_masked.track_variation it multiplies a
+    [B, pairs] tensor by a [B,H,W,1] mask."""
+    tj = training_json
+    stat, masked, loaded = _levels(arch, tj)
+    for level, m in zip(_LEVELS, masked):
+        if m["track_variation_difference_histogram"]:
+            raise ValueError("%s.statistics_masked.track_variation_difference_histogram cannot be tracked: the reference multiplies the "
+                             "[B, pairs] variation difference by the [B,H,W,1] mask (BaseFeatureTraining.masked_variation_difference, "
+                             "Training.py:146-149), which has no meaning" % level)
+    scales = range(arch.number_of_scales() if tj["use_multiscale_metrics"] else 1)
+    plan = []
+
+    def add(source, name, s, m, has_mask):
+        for k in scales:
+            if s["track_difference_histogram"]:
+                plan.append(HistogramEntry(Naming.difference_name(name, scale_index=k), source, "difference", k))
+            if s["track_variation_difference_histogram"]:
+                plan.append(HistogramEntry(Naming.variation_difference_name(name, scale_index=k), source, "variation_difference", k))
+            if m["track_difference_histogram"] and has_mask:
+                plan.append(HistogramEntry(Naming.difference_name(name, masked=True, scale_index=k), source, "masked_difference", k))
+
+    for f in loaded:
+        add(("feature", f.name), f.name, stat[0], masked[0], mask_pass(f.name) is not None)
+    use_image, use_comb = combined_levels(tj)
+    if use_comb:
+        for cname, _ in combined_triples(arch):
+            add(("combined", cname), cname, stat[1], masked[1], True)
+    if use_image:
+        add(("image", IMAGE_NAME), IMAGE_NAME, stat[2], _flags(None), False)
+    return plan
+
+
+def decode_histogram_records(raw, n, nb):
+    """n device records (include/dd_hip.h: uint32 counts[nb] | double min, max, sum, sum_squares | uint64 num, nonfinite) as a host TABLE:
+    {"counts": int64 [n, nb], "min" / "max" / "sum" / "sum_squares": float64 [n], "num" / "nonfinite": int64 [n]}."""
+    off = (nb + 1) // 2 * 8
+    raw = np.ascontiguousarray(np.asarray(raw, dtype=np.uint8).reshape(n, off + 48))
+    stats = np.ascontiguousarray(raw[:, off:off + 32]).view(np.float64)
+    nums = np.ascontiguousarray(raw[:, off + 32:off + 48]).view(np.uint64).astype(np.int64)
+    table = {"counts": np.ascontiguousarray(raw[:, :4 * nb]).view(np.uint32).astype(np.int64)}
+    table.update({k: stats[:, j].copy() for j, k in enumerate(_STAT_KEYS)})
+    table["num"], table["nonfinite"] = nums[:, 0].copy(), nums[:, 1].copy()
+    return table
+
+
+_ADD_KEYS = ("counts", "num", "nonfinite", "sum", "sum_squares")
+
+
+def histogram_reduce_pack(table):
+    """A table as the two float64 vectors a merge works on: `adds` (counts, num, nonfinite, sum, sum_squares: they ADD; a count is exact in
+    a double up to 2^53) and `ext` ([max, -min]: the element-wise MAXIMUM is taken).  train.py all-reduces them (SUM, MAX)."""
+    adds = np.concatenate([np.asarray(table[k], dtype=np.float64).reshape(-1) for k in _ADD_KEYS])
+    ext = np.concatenate([np.asarray(table["max"], dtype=np.float64), -np.asarray(table["min"], dtype=np.float64)])
+    return adds, ext
+
+
+def histogram_reduce_unpack(adds, ext, n, nb):
+    """The table of n records with nb buckets from reduced `adds` / `ext` vectors."""
+    adds, ext = np.asarray(adds, dtype=np.float64), np.asarray(ext, dtype=np.float64)
+    assert adds.size == n * nb + 4 * n and ext.size == 2 * n, "not the vectors of histogram_reduce_pack"
+    table, at = {}, 0
+    for k in _ADD_KEYS:
+        size = n * nb if k == "counts" else n
+        part = adds[at:at + size]
+        table[k] = part.copy() if k in ("sum", "sum_squares") else np.rint(part).astype(np.int64)
+        at += size
+    table["counts"] = table["counts"].reshape(n, nb)
+    table["max"], table["min"] = ext[:n].copy(), -ext[n:]
+    return table
+
+
+def merge_histogram_tables(tables):
+    """The table of the values of all `tables` together (the ranks of a data-parallel run): counts, num, nonfinite, sum and sum_squares add,
+    min / max are taken -- the SUM and the MAX that train.py's two all-reduces apply to the vectors of histogram_reduce_pack."""
+    packed = [histogram_reduce_pack(t) for t in tables]
+    n, nb = tables[0]["counts"].shape
+    return histogram_reduce_unpack(np.sum([a for a, _ in packed], axis=0), np.max([e for _, e in packed], axis=0), n, nb)
+
+
+def compress_buckets(limits, counts):
+    """Histogram::EncodeToProto without preserve_zero_buckets: every non-empty bucket is an entry (its limit, its count); a run of empty
+    buckets collapses into ONE entry with the limit of the run's last bucket and a count of 0 (an all-empty histogram: (DBL_MAX, 0))."""
+    counts = np.asarray(counts)
+    keep = counts > 0
+    keep[:-1] |= counts[1:] > 0      # the last bucket of a run of empty ones: its successor is not empty ...
+    keep[-1] = True                  # ... or it is the last bucket
+    return [float(x) for x in np.asarray(limits)[keep]], [float(c) for c in counts[keep]]
+
+
+def histogram_values(plan, table, limits=None, out=print):
+    """[(tag, {"min", "max", "num", "sum", "sum_squares", "bucket_limit", "bucket"})] of `plan` from a table whose row i belongs to plan[i]:
+    the fields of a HistogramProto.  tf.summary.histogram fails the run on a NaN or inf; here a tag whose record counted a non-finite value
+    is LEFT OUT for this step (said once per tag through `out`): a skipped fp16 step must not end the training."""
+    limits = histogram_limits() if limits is None else limits
+    res = []
+    for i, e in enumerate(plan):
+        if int(table["nonfinite"][i]) > 0:
+            if e.tag not in _said_nonfinite:
+                _said_nonfinite.add(e.tag)
+                out("histogram %s: %d value(s) are inf or NaN -- not written for this step (said once per tag)" % (e.tag, int(table["nonfinite"][i])))
+            continue
+        bl, bc = compress_buckets(limits, table["counts"][i])
+        h = {k: float(table[k][i]) for k in _STAT_KEYS}
+        h.update(num=float(table["num"][i]), bucket_limit=bl, bucket=bc)
+        res.append((e.tag, h))
+    return res
 
 
 class MeanAccumulator:

@@ -13,7 +13,10 @@ Summaries (metrics.py, summaries.py): every `--summary_steps` steps (100 = the E
 `loss`, `learning_rate`, `batch_size` (Training.py:676-677) and the tracked scalars of Training.json's statistics sections (Training.py:688-698)
 for the current mini-batch into a TensorBoard event file in the model directory; a validation pass averages the same metrics over the
 validation set (eval_metric_ops, Training.py:704-719), prints them and writes them with `loss` into <model_directory>/eval_<validation json stem>/
-(estimator.evaluate(name=...), Training.py:874-877).  Not reproduced: histogram and image summaries."""
+(estimator.evaluate(name=...), Training.py:874-877).  With `--histograms` the same training event also carries the histograms the
+*_histogram flags of the statistics sections ask for (tf.summary.histogram, Training.py:679-686; metrics.histogram_plan), binned on the device
+from the forward that yields the tracked scalars; validation passes write none (the reference adds them in TRAIN mode only).  Without the
+flag the *_histogram keys are read and, said once, not written.  Not reproduced: image summaries, histograms of weights or gradients."""
 import argparse
 import json
 import multiprocessing
@@ -47,6 +50,9 @@ def parser():
     p.add_argument("--dtype", default="bf16", choices=["bf16", "f16", "f32"], help="storage type of activations (accumulation is fp32)")
     p.add_argument("--summary_steps", type=int, default=100,
                    help="Write the loss and the tracked metrics of the current mini-batch as TensorBoard scalars every this many steps (0: never).")
+    p.add_argument("--histograms", action="store_true",
+                   help="Also write the histograms that the *_histogram flags of Training.json ask for, every --summary_steps steps "
+                        "(binned on the device; a tag with an inf / NaN value is left out for that step).")
     p.add_argument("--loss_scale", type=loss_scale.cli_value, default=None, metavar="{dynamic,<number>}",
                    help="Loss scale of the optimisation step: 'dynamic' keeps it on the device (halved on an inf / NaN gradient, whose step is skipped, "
                         "doubled after 2000 applied steps), a positive number fixes it.  Default: 4096 for f16, 1 for bf16 / f32.")
@@ -339,17 +345,37 @@ def main(args):
         return
 
     writer = summaries.EventFileWriter(model_dir) if (rank == 0 and args.summary_steps > 0) else None
+    trainer.program.write_histograms = bool(args.histograms)
+    hist_plan = trainer.program.histogram_plan() if (args.histograms and args.summary_steps > 0) else []
     names = [e.name for e in trainer.program.metric_plan()] if args.summary_steps > 0 else []
 
     def tracked_scalars():
         """The tracked metrics of the staged mini-batch at the current weights: a forward of its own BEFORE trainer.step() (the step is left
         as it is, and its backward may reuse prediction buffers).  Under data parallelism the per-image sums of all ranks are added, so
-        rank 0 logs the global batch."""
-        if not names:
-            return []
+        rank 0 logs the global batch.  The same forward yields the histograms (--histograms): (scalars, histograms)."""
+        if not names and not hist_plan:
+            return [], None
         prog = trainer.program
         prog.zero_grads()
         prog.forward()
+        records = prog.histogram_table() if hist_plan else None      # (launched now, read back behind the metric launches)
+        scalars = _scalars(prog) if names else []
+        return scalars, (tracked_histograms(prog, records) if hist_plan else None)
+
+    def tracked_histograms(prog, records):
+        """[(tag, HistogramProto fields)] of the forward just made.  Data parallelism: one SUM all-reduce over counts / num / nonfinite / sum /
+        sum_squares (float64: a count is exact up to 2^53) and one MAX all-reduce over [max, -min]; every rank takes part, rank 0 writes."""
+        from . import metrics as M
+        table = prog.histogram_host_table(records)
+        if world > 1:
+            adds, ext = (torch.from_numpy(v).to(arch.device) for v in M.histogram_reduce_pack(table))
+            dist.all_reduce(adds)
+            dist.all_reduce(ext, op=dist.ReduceOp.MAX)
+            table = M.histogram_reduce_unpack(adds.cpu().numpy(), ext.cpu().numpy(), *table["counts"].shape)
+        st = prog._histograms_built()
+        return M.histogram_values(st["plan"], table, st["limits"], out=print if rank == 0 else (lambda *a: None))
+
+    def _scalars(prog):
         table = prog.metric_table()
         if world == 1:
             return list(zip(names, prog.metric_values(table)))
@@ -384,7 +410,7 @@ def main(args):
             nxt = next(it, None)                                         # the next mini-batch uploads while this step runs
             staged = uploader.stage(*nxt) if nxt is not None else None
             summary = args.summary_steps > 0 and (step + 1) % args.summary_steps == 0
-            scalars = tracked_scalars() if summary else None
+            scalars, histos = tracked_scalars() if summary else (None, None)
             loss = trainer.step()
             step += 1
             if summary:
@@ -395,8 +421,11 @@ def main(args):
                 if scaler is not None:
                     scalars = [("loss_scale", scaler["scale"]), ("skipped_steps", scaler["skipped_total"])] + scalars
                 if writer is not None:
-                    writer.add_scalars(step, [("loss", float(mean_loss) / world), ("learning_rate", tj["learning_rate"]),
-                                              ("batch_size", tj["batch_size"])] + scalars)
+                    head = [("loss", float(mean_loss) / world), ("learning_rate", tj["learning_rate"]), ("batch_size", tj["batch_size"])]
+                    if histos:      # ONE event: the scalars up to batch_size, the histograms, the tracked scalars (Training.py:676-698)
+                        writer.add_summaries(step, head, histos, scalars)
+                    else:
+                        writer.add_scalars(step, head + scalars)
             if step % 50 == 0 or staged is None:
                 total, count = total + float(loss), count + 1
         if dist is not None:

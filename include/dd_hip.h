@@ -461,6 +461,40 @@ int dd_loss_msssim_values(const dd_loss_msssim_desc* desc, int B, int H, int W, 
 long dd_loss_metrics_scratch_bytes(int B, int H, int W);
 int dd_loss_metrics(const dd_loss_desc* desc, int B, int H, int W, float* scratch, float* table, dd_stream stream);
 
+/* ---- TensorBoard histograms of the tracked differences (track_difference_histogram / track_variation_difference_histogram of the statistics
+ * sections: BaseFeatureTraining.add_tracked_histograms, Training.py:267-281; tf.summary.histogram -> tensorflow/core/lib/histogram/histogram.cc)
+ * (csrc/dd_histogram.hip).  A histogram RECORD is DD_HISTOGRAM_RECORD_BYTES(nb) bytes of device memory, 8-byte aligned:
+ *   uint32 counts[nb]                                   bucket b counts limits[b-1] <= x < limits[b]  (Histogram::Add: upper_bound)
+ *   at DD_HISTOGRAM_STATS_OFFSET(nb):  double min, max, sum, sum_squares;  uint64 num, nonfinite
+ * limits: nb doubles in DEVICE memory, strictly increasing, the last one above every fp32 -- the table the host later writes as bucket_limit
+ * (TensorFlow's default: 1551 entries); the device compares against it and never rebuilds it.  A NaN or +-inf value increments nonfinite and
+ * touches nothing else.  An empty histogram has min = DBL_MAX, max = -DBL_MAX.  Counts are integer atomics, sum / sum_squares are added in
+ * double in a fixed order, min / max do not depend on order: two runs give the same bits.  Records are OVERWRITTEN.  No host sync.  Counts are 32-bit: one call takes fewer
+ * than 2^32 values (dd_loss_histograms: 2 B H W < 2^32).  The bucket search starts from a guess made for TensorFlow's default table and ends
+ * in a binary search for any other table: exact for both, a few comparisons per value only for the default one. */
+#define DD_HISTOGRAM_MAX_BUCKETS 4096
+#define DD_HISTOGRAM_STATS_OFFSET(nb) ((((long)(nb) + 1) / 2) * 8)
+#define DD_HISTOGRAM_RECORD_BYTES(nb) (DD_HISTOGRAM_STATS_OFFSET(nb) + 48)
+#define DD_HISTOGRAM_VALUES_SCRATCH_BYTES 20480
+#define DD_HISTOGRAM_MAX_CHUNKS 32
+/* The binning primitive (what tf.summary.histogram does with the flat tensor it is given, Training.py:274): record = histogram of
+ * values[0 .. n), n > 0 fp32 values, 4-byte aligned.  scratch: DD_HISTOGRAM_VALUES_SCRATCH_BYTES, 8-byte aligned. */
+int dd_histogram_values(const float* values, long n, const double* limits, int nb, void* record, void* scratch, dd_stream stream);
+/* The tracked histograms of ONE scale, from the sources of a dd_loss_desc read exactly as dd_loss_metrics reads them.  selection: HOST array
+ * of n_records (slot, kind) pairs, slot as in the dd_loss_metrics table; record r (records + r * DD_HISTOGRAM_RECORD_BYTES(nb)) receives
+ *   DD_HISTOGRAM_DIFFERENCE            the channel-summed LossDifference of every pixel, B*H*W values                     (Training.py:116-119, :274)
+ *   DD_HISTOGRAM_VARIATION_DIFFERENCE  the H(W-1) horizontal and (H-1)W vertical pair differences of every image          (:139-176, :276)
+ *   DD_HISTOGRAM_MASKED_DIFFERENCE     difference * non-zero mask of mask_feature's target, B*H*W values, zeros included  (:121-124, :279)
+ * A masked difference needs mask_feature / comb_mask_feature >= 0 (the image has none); a pair may be selected once.  scratch:
+ * >= dd_loss_histograms_scratch_bytes, 8-byte aligned.  Values are formed in fp32 like dd_loss_metrics'.  desc is a HOST struct (copied by
+ * value). */
+#define DD_HISTOGRAM_DIFFERENCE 0
+#define DD_HISTOGRAM_VARIATION_DIFFERENCE 1
+#define DD_HISTOGRAM_MASKED_DIFFERENCE 2
+long dd_loss_histograms_scratch_bytes(int B, int H, int W, int n_records);
+int dd_loss_histograms(const dd_loss_desc* desc, int B, int H, int W, const int* selection, int n_records, const double* limits, int nb,
+                       void* records, void* scratch, dd_stream stream);
+
 /* ---- Adam, TensorFlow formulation (tf.train.AdamOptimizer, Training.py:701-702), flat arenas */
 int dd_adam_step(float* params, const float* grads, float* m, float* v, long n, float lr_t, float beta1, float beta2,
                  float eps, float grad_scale, dd_stream stream);
