@@ -17,6 +17,9 @@ METRIC_SOURCES = MAX_FEATURES + MAX_COMBINED + 1      # DD_METRIC_SOURCES: rows 
 # histogram records (dd_histogram_values / dd_loss_histograms): uint32 counts[nb] | double min, max, sum, sum_squares | uint64 num, nonfinite
 HISTOGRAM_DIFFERENCE, HISTOGRAM_VARIATION_DIFFERENCE, HISTOGRAM_MASKED_DIFFERENCE = 0, 1, 2
 HISTOGRAM_VALUES_SCRATCH_BYTES = 20480
+# dd_loss_previews: panel bits, the most images of one launch, the length of the threshold table
+PREVIEW_SOURCE, PREVIEW_PREDICTION, PREVIEW_TARGET, PREVIEW_DIFFERENCE = 1, 2, 4, 8
+PREVIEW_MAX_IMAGES, PREVIEW_THRESHOLDS = 16, 255
 
 
 def histogram_stats_offset(nb):
@@ -42,7 +45,7 @@ SYMBOLS = (
     "dd_loss_msssim_scratch_bytes", "dd_loss_msssim_fwd", "dd_loss_msssim_bwd", "dd_loss_msssim_values",
     "dd_loss_metrics_scratch_bytes", "dd_loss_metrics", "dd_loss_head_path_count",
     "dd_loss_head_dscale", "dd_loss_msssim_bwd_dscale", "dd_grads_nonfinite", "dd_adam_step_scaled", "dd_scaler_update",
-    "dd_histogram_values", "dd_loss_histograms_scratch_bytes", "dd_loss_histograms",
+    "dd_histogram_values", "dd_loss_histograms_scratch_bytes", "dd_loss_histograms", "dd_loss_previews",
 )
 
 
@@ -300,6 +303,8 @@ def load():
     lib.dd_loss_histograms_scratch_bytes.argtypes = [i, i, i, i]
     lib.dd_loss_histograms_scratch_bytes.restype = C.c_long
     lib.dd_loss_histograms.argtypes = [C.POINTER(LossDesc), i, i, i, C.POINTER(C.c_int), i, vp, i, vp, vp, vp]
+    lib.dd_loss_previews.argtypes = [C.POINTER(LossDesc), C.POINTER(vp), C.POINTER(C.c_int), i, i, i, C.POINTER(C.c_int), i, C.POINTER(C.c_int), i, i, vp, f, f,
+                                     vp, vp]
     lib.dd_adam_step.argtypes = [vp, vp, vp, vp, l, f, f, f, f, f, vp]
     lib.dd_loss_head_dscale.argtypes = [C.POINTER(LossDesc), i, i, i, vp, vp, vp]
     lib.dd_loss_msssim_bwd_dscale.argtypes = [C.POINTER(MsSsimDesc), i, i, i, vp, vp, vp]

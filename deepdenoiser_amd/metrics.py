@@ -13,6 +13,11 @@ histogram_values turn the device records of dd_histogram_values / dd_loss_histog
 restated from tensorflow/core/lib/histogram/histogram.cc (PARITY UNPINNED, like ssim_multiscale and the event format).  The launches are
 Program.histograms(); `python -m deepdenoiser_amd.train --histograms` writes them.  metric_plan alone still says once that the flags are set
 and nothing is written, unless its caller passes histograms=True.
+
+Image summaries (new functionality: the reference writes none): preview_plan lists the sources whose source | prediction | target previews
+dd_loss_previews (include/dd_hip.h) renders, preview_thresholds is the table it compares against -- the sRGB transfer function lives here,
+on the host, the device only counts table entries --, preview_tags names the images the way TF 1.x's tf.summary.image does.  The launch is
+Program.previews(); `python -m deepdenoiser_amd.train --image_steps N` writes them.
 """
 import collections
 
@@ -306,6 +311,83 @@ def histogram_values(plan, table, limits=None, out=print):
         h.update(num=float(table["num"][i]), bucket_limit=bl, bucket=bc)
         res.append((e.tag, h))
     return res
+
+
+# ---------------------------------------------------------------------------------------------------------------- image summaries
+PreviewEntry = collections.namedtuple("PreviewEntry", "name source")
+# source as in MetricEntry; name: what the tag carries (previews/<name>/image[/<k>])
+PREVIEW_PANELS = ("source", "prediction", "target", "difference")      # bit k of dd_loss_previews' panel mask
+_IMAGE_COMBINED = ("Diffuse", "Glossy", "Subsurface", "Transmission")                          # CombinedImageFeatureTraining.initialize,
+_IMAGE_SINGLE = ("Volume Direct", "Volume Indirect", "Emission", "Environment")                # Training.py:475-495
+
+
+def srgb_oetf(x):
+    """The sRGB opto-electronic transfer function (IEC 61966-2-1) of linear values in [0, 1], float64."""
+    x = np.asarray(x, dtype=np.float64)
+    return np.where(x <= 0.0031308, 12.92 * x, 1.055 * np.power(np.maximum(x, 0.0), 1.0 / 2.4) - 0.055)
+
+
+def srgb_inverse_oetf(y):
+    """The inverse of srgb_oetf on [0, 1], float64."""
+    y = np.asarray(y, dtype=np.float64)
+    return np.where(y <= 12.92 * 0.0031308, y / 12.92, np.power((np.maximum(y, 0.0) + 0.055) / 1.055, 2.4))
+
+
+def preview_thresholds():
+    """The 255 fp32 thresholds of an 8-bit sRGB display value: entry k-1 is the linear value at which round(255 * OETF) steps from k-1 to k,
+    the inverse OETF of (k - 0.5) / 255, k = 1 .. 255, computed in float64 and rounded to fp32 (strictly increasing in fp32).  The byte of a
+    value v is the number of entries <= v: below the first is 0, at or above the last 255, so the table clamps by construction."""
+    k = np.arange(1, 256, dtype=np.float64)
+    return srgb_inverse_oetf((k - 0.5) / 255.0).astype(np.float32)
+
+
+def image_members(arch):
+    """(combined names, single pass names) the combined image sums, when the architecture defines all four combined features and the single
+    passes (CombinedImageFeatureTraining.initialize, Training.py:475-495); None otherwise."""
+    targets = {f.name for f in arch.feature_predictions if f.is_target}
+    combined = {c for c, _ in combined_triples(arch)}
+    if all(c in combined for c in _IMAGE_COMBINED) and all(n in targets for n in _IMAGE_SINGLE):
+        return _IMAGE_COMBINED, _IMAGE_SINGLE
+    return None
+
+
+def preview_plan(arch, training_json=None, which="combined"):
+    """The ordered list of PreviewEntry of an image summary.  which = "combined": the combined image (when image_members(arch) exists), then
+    every combined feature; "all": these, then every predicted pass that is loaded (a generated pass has nothing to show).  "combined" on an
+    architecture without combined features means "all".  The plan depends on the architecture alone: a preview shows a source whether or
+    not a loss weight or a tracked statistic of `training_json` uses it."""
+    if which not in ("combined", "all"):
+        raise ValueError("previews: which = %r ('combined' or 'all')" % (which,))
+    plan = []
+    triples = combined_triples(arch)
+    if image_members(arch) is not None:
+        plan.append(PreviewEntry(Naming.tensorboard_name(IMAGE_NAME), ("image", IMAGE_NAME)))
+    for cname, _ in triples:      # named like the statistics of a combined feature (Naming._statistics_name): "Combined <name>"
+        plan.append(PreviewEntry(Naming.tensorboard_name("Combined " + cname), ("combined", cname)))
+    if which == "all" or not plan:
+        for f in arch.feature_predictions:
+            if f.is_target and f.load_data:
+                plan.append(PreviewEntry(Naming.tensorboard_name(f.name), ("feature", f.name)))
+    return plan
+
+
+def preview_tags(name, count):
+    """TF 1.x's tf.summary.image convention: <name>/image for a single image, <name>/image/<k> for several."""
+    base = "previews/%s/image" % name
+    return [base] if count == 1 else ["%s/%d" % (base, k) for k in range(count)]
+
+
+def preview_panel_mask(panels):
+    """The panel bit mask of dd_loss_previews from names of PREVIEW_PANELS (the mosaic shows them in PREVIEW_PANELS order, whatever the
+    order given)."""
+    mask = 0
+    for p in panels:
+        if p not in PREVIEW_PANELS:
+            raise ValueError("previews: unknown panel %r (one of %s)" % (p, ", ".join(PREVIEW_PANELS)))
+        mask |= 1 << PREVIEW_PANELS.index(p)
+    if not mask:
+        raise ValueError("previews: no panel asked for")
+    return mask
 
 
 class MeanAccumulator:

@@ -16,7 +16,14 @@ validation set (eval_metric_ops, Training.py:704-719), prints them and writes th
 (estimator.evaluate(name=...), Training.py:874-877).  With `--histograms` the same training event also carries the histograms the
 *_histogram flags of the statistics sections ask for (tf.summary.histogram, Training.py:679-686; metrics.histogram_plan), binned on the device
 from the forward that yields the tracked scalars; validation passes write none (the reference adds them in TRAIN mode only).  Without the
-flag the *_histogram keys are read and, said once, not written.  Not reproduced: image summaries, histograms of weights or gradients."""
+flag the *_histogram keys are read and, said once, not written.
+
+Image summaries (new: the reference writes none): with `--image_steps N` rank 0 renders, every N steps, the first `--image_count` examples of
+its staged mini-batch as source | prediction | target [| difference, `--image_difference`] previews of the sources `--images` names
+(metrics.preview_plan), on the device from the pre-step forward (shared with the tracked scalars when both fall on one step), and writes them
+as ONE event of their own that holds only the images.  Every validation pass then also writes the previews of the first examples of each
+validation set's first mini-batch into that set's eval_<name> event file at the global step: that stream is not shuffled, so the same
+tiles appear every epoch.  No collective: the other ranks do nothing.  Not reproduced: histograms of weights or gradients."""
 import argparse
 import json
 import multiprocessing
@@ -53,6 +60,14 @@ def parser():
     p.add_argument("--histograms", action="store_true",
                    help="Also write the histograms that the *_histogram flags of Training.json ask for, every --summary_steps steps "
                         "(binned on the device; a tag with an inf / NaN value is left out for that step).")
+    p.add_argument("--image_steps", type=int, default=0,
+                   help="Write image summaries (source | prediction | target previews, rendered on the device) every this many steps and "
+                        "with every validation pass (0: never).")
+    p.add_argument("--images", default="combined", choices=["combined", "all"],
+                   help="Which sources get a preview: the combined image and the combined features, or also every predicted pass.")
+    p.add_argument("--image_count", type=int, default=3, help="Examples of the mini-batch per preview (tf.summary.image's max_outputs).")
+    p.add_argument("--image_exposure", type=float, default=1.0, help="Factor applied to the values of a preview before the sRGB quantisation.")
+    p.add_argument("--image_difference", action="store_true", help="Add a fourth panel: the absolute loss difference of prediction and target.")
     p.add_argument("--loss_scale", type=loss_scale.cli_value, default=None, metavar="{dynamic,<number>}",
                    help="Loss scale of the optimisation step: 'dynamic' keeps it on the device (halved on an inf / NaN gradient, whose step is skipped, "
                         "doubled after 2000 applied steps), a positive number fixes it.  Default: 4096 for f16, 1 for bf16 / f32.")
@@ -242,10 +257,26 @@ class Uploader:
         return df, dl, done, (feats, labels)                            # (the pinned sources stay alive until the copy has run)
 
 
-def run_validation(trainer, arch, tj, base, B, rank, world, threads, metrics_out=None):
+def preview_settings(args, B):
+    """The keyword arguments of Program.preview_table for the command line's --image_* flags, or None when image summaries are off."""
+    if args.image_steps <= 0:
+        return None
+    if not 1 <= args.image_count <= 16:
+        raise ValueError("--image_count %d: 1 .. 16 examples fit one preview launch" % args.image_count)
+    panels = ("source", "prediction", "target") + (("difference",) if args.image_difference else ())
+    return {"images": list(range(min(args.image_count, B))), "which": args.images, "panels": panels, "exposure": args.image_exposure}
+
+
+def preview_summaries(prog, table, preview):
+    """[(tag, height, width, colorspace, png)] of a preview table (Program.preview_table): one copy from the device, one PNG per image."""
+    return [summaries.image_summary(tag, a) for tag, a in prog.preview_images(table, preview["images"], preview["which"])]
+
+
+def run_validation(trainer, arch, tj, base, B, rank, world, threads, metrics_out=None, previews_out=None, preview=None):
     """Training.py:1230-1250 / :1264-1284: every validation*.json, tiles of base/validation/<spp>/, no augmentation, mean loss.
     metrics_out: a dict that receives {validation json stem: [(metric name, mean over the set)]} -- the tracked metrics of every mini-batch
-    (program.metrics over its real examples), averaged with the weights the loss gets."""
+    (program.metrics over its real examples), averaged with the weights the loss gets.  previews_out (with `preview`, preview_settings): a
+    dict that receives {stem: image summaries of the first examples of the set's first mini-batch} -- on the rank that passes it only."""
     import torch.distributed as dist
     results = []
     plan = trainer.program.metric_plan() if metrics_out is not None else []
@@ -270,6 +301,8 @@ def run_validation(trainer, arch, tj, base, B, rank, world, threads, metrics_out
             losses.append(trainer.program.loss_buf.double().sum())
             if plan:      # (a copy on the device: how many of the LAST mini-batch are real is known only when the stream has ended)
                 tables.append(trainer.program.metric_table().clone())
+            if previews_out is not None and preview is not None and len(losses) == 1:
+                previews_out[os.path.splitext(name)[0]] = preview_summaries(trainer.program, trainer.program.preview_table(**preview), preview)
         # every example counts once: a mini-batch's mean is weighed by its REAL examples (the last round of the epoch is filled with repeats)
         for i, l in enumerate(losses):
             w = stream.real_in_last if (stream.padded and i == len(losses) - 1) else B
@@ -325,9 +358,12 @@ def main(args):
 
     eval_writers = {}
 
+    preview = preview_settings(args, B)
+
     def report_validation(tag):
-        tracked = {}
-        for name, loss, n in run_validation(trainer, arch, tj, base, B, rank, world, args.threads, metrics_out=tracked):
+        tracked, shown = {}, ({} if (preview is not None and rank == 0) else None)
+        for name, loss, n in run_validation(trainer, arch, tj, base, B, rank, world, args.threads, metrics_out=tracked, previews_out=shown,
+                                            preview=preview):
             if rank == 0:
                 print("%s: %s loss %.5f over %d batches" % (tag, name, loss, n))
                 for metric, value in tracked.get(name, []):
@@ -335,6 +371,8 @@ def main(args):
                 if name not in eval_writers:      # estimator.evaluate(name=name): one event file per run and validation set
                     eval_writers[name] = summaries.EventFileWriter(os.path.join(model_dir, "eval_" + name))
                 eval_writers[name].add_scalars(step, [("loss", loss)] + tracked.get(name, []))
+                if shown and name in shown:
+                    eval_writers[name].add_images(step, shown[name])
 
     if args.validate:                                                     # Training.py:1230: a validation-only run
         report_validation("validation")
@@ -344,20 +382,26 @@ def main(args):
             dist.destroy_process_group()
         return
 
-    writer = summaries.EventFileWriter(model_dir) if (rank == 0 and args.summary_steps > 0) else None
+    writer = summaries.EventFileWriter(model_dir) if (rank == 0 and (args.summary_steps > 0 or preview is not None)) else None
     trainer.program.write_histograms = bool(args.histograms)
     hist_plan = trainer.program.histogram_plan() if (args.histograms and args.summary_steps > 0) else []
     names = [e.name for e in trainer.program.metric_plan()] if args.summary_steps > 0 else []
 
-    def tracked_scalars():
-        """The tracked metrics of the staged mini-batch at the current weights: a forward of its own BEFORE trainer.step() (the step is left
-        as it is, and its backward may reuse prediction buffers).  Under data parallelism the per-image sums of all ranks are added, so
-        rank 0 logs the global batch.  The same forward yields the histograms (--histograms): (scalars, histograms)."""
-        if not names and not hist_plan:
-            return [], None
+    def pre_step_forward():
         prog = trainer.program
         prog.zero_grads()
         prog.forward()
+
+    def tracked_scalars(forwarded=False):
+        """The tracked metrics of the staged mini-batch at the current weights: a forward of its own BEFORE trainer.step() (the step is left
+        as it is, and its backward may reuse prediction buffers; forwarded: the image summaries of this step have made it already).  Under
+        data parallelism the per-image sums of all ranks are added, so rank 0 logs the global batch.  The same forward yields the
+        histograms (--histograms): (scalars, histograms)."""
+        if not names and not hist_plan:
+            return [], None
+        prog = trainer.program
+        if not forwarded:
+            pre_step_forward()
         records = prog.histogram_table() if hist_plan else None      # (launched now, read back behind the metric launches)
         scalars = _scalars(prog) if names else []
         return scalars, (tracked_histograms(prog, records) if hist_plan else None)
@@ -410,9 +454,18 @@ def main(args):
             nxt = next(it, None)                                         # the next mini-batch uploads while this step runs
             staged = uploader.stage(*nxt) if nxt is not None else None
             summary = args.summary_steps > 0 and (step + 1) % args.summary_steps == 0
-            scalars, histos = tracked_scalars() if summary else (None, None)
+            # image summaries: rank 0 alone, launched on the pre-step forward (made here, shared with the tracked scalars), read back behind
+            # the step like the histogram records
+            show = preview is not None and rank == 0 and (step + 1) % args.image_steps == 0
+            shown = None
+            if show:
+                pre_step_forward()
+                shown = trainer.program.preview_table(**preview)
+            scalars, histos = tracked_scalars(forwarded=show) if summary else (None, None)
             loss = trainer.step()
             step += 1
+            if shown is not None:
+                writer.add_images(step, preview_summaries(trainer.program, shown, preview))
             if summary:
                 mean_loss = loss.double().sum()
                 if dist is not None:

@@ -495,6 +495,33 @@ long dd_loss_histograms_scratch_bytes(int B, int H, int W, int n_records);
 int dd_loss_histograms(const dd_loss_desc* desc, int B, int H, int W, const int* selection, int n_records, const double* limits, int nb,
                        void* records, void* scratch, dd_stream stream);
 
+/* ---- image summaries: 8-bit previews of source | prediction | target | difference of ONE scale, rendered on the device
+ * (csrc/dd_preview.hip; the reference writes no image summaries).  Reads the sources of a dd_loss_desc as dd_loss_metrics reads them -- pred /
+ * target, pred_ld / target_ld, nch (1 or 3), comb, image_combined / image_features, kind, epsilon; weights, dpred, masks and the pred_std
+ * fusion fields are ignored -- plus `source`: per feature the raw noisy pass [B,H,W,source_ld[f]], its first nch[f] channels used (HOST arrays
+ * of n_features entries; may be NULL without the source panel).
+ *   images : HOST, n_images batch indices 0 <= b < B (1 .. DD_PREVIEW_MAX_IMAGES, repeats allowed)
+ *   slots  : HOST, n_slots source slots as in the dd_loss_metrics table (1 .. DD_METRIC_SOURCES)
+ *   panels : bit mask of DD_PREVIEW_SOURCE / PREDICTION / TARGET / DIFFERENCE, P = the number of set bits
+ * out: n_slots mosaics, each [n_images * H, P * W, 3] uint8 RGB: image row r is batch image images[r], panels run left to right in bit order.
+ * A source / prediction / target panel pixel is the slot's value formed from that set of tensors (a feature's own channels, a 1-channel pass
+ * replicated to gray; combined = color * (direct + indirect); image = sum of its members: the helpers of the loss kernels, one fp32 rounding
+ * per operation), multiplied once by `exposure`.  The difference panel is gray: |channel-summed LossDifference(pred, target)| * error_gain.
+ * A byte is the number of entries of `thresholds` (DEVICE, DD_PREVIEW_THRESHOLDS fp32, strictly increasing) that are <= the value: the host
+ * owns the transfer function, the device only compares.  +inf gives 255, -inf 0; a NaN in any channel makes the pixel (255, 0, 255).
+ * One launch, plain stores, every byte of the mosaics written exactly once and no other: two runs give the same bits.  A bad argument (a slot
+ * the descriptor does not have, n_images / n_slots out of range, panels == 0, a NULL source with the source bit set, a NULL table) returns a
+ * negative status without a launch.  desc is a HOST struct (copied by value).  No host sync. */
+#define DD_PREVIEW_MAX_IMAGES 16
+#define DD_PREVIEW_THRESHOLDS 255
+#define DD_PREVIEW_SOURCE 1
+#define DD_PREVIEW_PREDICTION 2
+#define DD_PREVIEW_TARGET 4
+#define DD_PREVIEW_DIFFERENCE 8
+int dd_loss_previews(const dd_loss_desc* desc, const float* const* source, const int* source_ld, int B, int H, int W, const int* images, int n_images,
+                     const int* slots, int n_slots, int panels, const float* thresholds, float exposure, float error_gain, unsigned char* out,
+                     dd_stream stream);
+
 /* ---- Adam, TensorFlow formulation (tf.train.AdamOptimizer, Training.py:701-702), flat arenas */
 int dd_adam_step(float* params, const float* grads, float* m, float* v, long n, float lr_t, float beta1, float beta2,
                  float eps, float grad_scale, dd_stream stream);
