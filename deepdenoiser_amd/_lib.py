@@ -20,6 +20,7 @@ HISTOGRAM_VALUES_SCRATCH_BYTES = 20480
 # dd_loss_previews: panel bits, the most images of one launch, the length of the threshold table
 PREVIEW_SOURCE, PREVIEW_PREDICTION, PREVIEW_TARGET, PREVIEW_DIFFERENCE = 1, 2, 4, 8
 PREVIEW_MAX_IMAGES, PREVIEW_THRESHOLDS = 16, 255
+NONFINITE_MAX_PLANES = 32      # DD_NONFINITE_MAX_PLANES
 
 
 def histogram_stats_offset(nb):
@@ -46,6 +47,7 @@ SYMBOLS = (
     "dd_loss_metrics_scratch_bytes", "dd_loss_metrics", "dd_loss_head_path_count",
     "dd_loss_head_dscale", "dd_loss_msssim_bwd_dscale", "dd_grads_nonfinite", "dd_adam_step_scaled", "dd_scaler_update",
     "dd_histogram_values", "dd_loss_histograms_scratch_bytes", "dd_loss_histograms", "dd_loss_previews",
+    "dd_nonfinite_scan", "dd_nonfinite_repair",
 )
 
 
@@ -211,6 +213,14 @@ class RecombineDesc(C.Structure):
                 ("combined", C.c_void_p * 4), ("n_singles", C.c_int), ("single", C.c_void_p * 8), ("image", C.c_void_p)]
 
 
+class NonfinitePlane(C.Structure):      # dd_nonfinite_plane
+    _fields_ = [("data", C.c_void_p), ("C", C.c_int), ("ld", C.c_int), ("mask", C.c_void_p)]
+
+
+class NonfiniteDesc(C.Structure):       # dd_nonfinite_desc
+    _fields_ = [("n_planes", C.c_int), ("plane", NonfinitePlane * NONFINITE_MAX_PLANES)]
+
+
 _lib = None
 
 
@@ -311,6 +321,8 @@ def load():
     lib.dd_grads_nonfinite.argtypes = [vp, l, vp, vp]
     lib.dd_adam_step_scaled.argtypes = [vp, vp, vp, vp, l, C.c_double, C.c_double, C.c_double, f, f, vp, vp]
     lib.dd_scaler_update.argtypes = [vp, f, f, i, f, f, vp]
+    lib.dd_nonfinite_scan.argtypes = [C.POINTER(NonfiniteDesc), i, i, i, vp, vp]
+    lib.dd_nonfinite_repair.argtypes = [C.POINTER(NonfiniteDesc), i, i, i, i, vp, vp]
     lib.dd_stitch.argtypes = [vp, i, i, vp, i, i, i, i, vp, i, vp]
     lib.dd_recombine.argtypes = [C.POINTER(RecombineDesc), l, vp]
     lib.dd_probe_tr16.argtypes = [vp, vp, vp, vp]

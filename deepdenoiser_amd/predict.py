@@ -11,7 +11,9 @@ import torch
 
 from . import openexr, tf_checkpoint
 from .architecture import Architecture
+from .nonfinite import Scanner, mask_to_rgb
 from .prediction import Predictor
+from .summaries import encode_png
 
 
 def parser():
@@ -26,7 +28,27 @@ def parser():
     p.add_argument("--dtype", default="f16", choices=["bf16", "f16", "f32"], help="storage type of activations (f32: the 1e-4 parity path)")
     p.add_argument("--tiles_per_batch", type=int, default=256)
     p.add_argument("--exr", action="store_true", help="also write <Pass>.exr")
+    p.add_argument("--nonfinite", default="keep", choices=["keep", "error", "repair"],
+                   help="NaN / Inf samples in the input passes: keep them (a whole tile of the output turns NaN), stop with an error that names "
+                        "the passes, or repair each from the finite values around it before denoising")
+    p.add_argument("--nonfinite_png", action="store_true", help="write <Pass>_nonfinite.png next to the inputs for every pass with NaN / Inf samples")
     return p
+
+
+def report_nonfinite(source, directory, write_png):
+    """One line per affected pass (name, values, pixels); with write_png also <Pass>_nonfinite.png: 8-bit RGB, channel c is 255 where the
+    mask bit c is set (a 1-channel pass replicated), from the device mask planes.  `source`: a Predictor or a nonfinite.Scanner."""
+    scanner = source._scanner if isinstance(source, Predictor) else source
+    masks = scanner.masks()
+    for (name, counts), channels in zip(scanner.report().items(), scanner.channels):
+        if not counts["values"]:
+            continue
+        print("%s: %d non-finite values in %d pixels" % (name, counts["values"], counts["pixels"]))
+        if write_png:
+            path = os.path.join(directory, name.rsplit("/", 1)[-1] + "_nonfinite.png")
+            with open(path, "wb") as f:
+                f.write(encode_png(mask_to_rgb(masks[name], channels).cpu().numpy()))
+            print(path)
 
 
 def main(args):
@@ -36,7 +58,9 @@ def main(args):
     feats = openexr.load_frame(args.input, arch)                                   # Prediction.py:223-252
     first = next(iter(feats.values()))
     height, width = first.shape[0], first.shape[1]
-    predictor = Predictor(arch, tile_size=int(args.tile_size), tile_overlap_size=int(args.tile_overlap_size), tiles_per_batch=args.tiles_per_batch)
+    mode = args.nonfinite
+    predictor = Predictor(arch, tile_size=int(args.tile_size), tile_overlap_size=int(args.tile_overlap_size), tiles_per_batch=args.tiles_per_batch,
+                          nonfinite=mode)
     predictor.prepare(height, width)                                               # raises for frames smaller than 16 pixels (Prediction.py:259-261)
     directory = os.path.dirname(os.path.abspath(args.json_filename))
     model_dir = aj["model_directory"] if os.path.isabs(aj["model_directory"]) else os.path.join(directory, aj["model_directory"])
@@ -44,7 +68,20 @@ def main(args):
     if latest is None:
         raise SystemExit("no checkpoint in %s (train first: python -m deepdenoiser_amd.train ...)" % model_dir)
     tf_checkpoint.load_variables(arch, latest, load_optimizer=False)               # Prediction.py:497-505 restores the Estimator's latest checkpoint
-    out = predictor.predict_frame({k: torch.from_numpy(np.ascontiguousarray(v)) for k, v in feats.items()})
+    frame = {k: torch.from_numpy(np.ascontiguousarray(v)) for k, v in feats.items()}
+    try:
+        out = predictor.predict_frame(frame)
+    except ValueError:
+        if mode != "error" or predictor._scanner is None:
+            raise
+        report_nonfinite(predictor, args.input, args.nonfinite_png)
+        raise SystemExit("non-finite values in the input passes (--nonfinite repair denoises the frame anyway)")
+    if mode == "repair":
+        report_nonfinite(predictor, args.input, args.nonfinite_png)
+    elif args.nonfinite_png:      # "keep": the prediction is today's; the frame is scanned for the pictures alone
+        scanner = Scanner(arch.device, [(k, tuple(v.shape)) for k, v in frame.items()])
+        scanner.scan({k: v.to(arch.device) for k, v in frame.items()})
+        report_nonfinite(scanner, args.input, True)
     for path in openexr.save_predictions(args.input, out, as_exr=args.exr):        # Prediction.py:483-510
         print(path)
 

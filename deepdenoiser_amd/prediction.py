@@ -21,7 +21,17 @@ _SINGLES = ("Volume Direct", "Volume Indirect", "Environment", "Emission")
 
 
 class Predictor:
-    def __init__(self, architecture, tile_size=128, tile_overlap_size=14, tiles_per_batch=16, use_graph=True):
+    def __init__(self, architecture, tile_size=128, tile_overlap_size=14, tiles_per_batch=16, use_graph=True, nonfinite="keep", nonfinite_radius=2):
+        """nonfinite: what to do about NaN / Inf samples in the source passes of a frame (nonfinite.py).  "keep": nothing -- no scan, no launch,
+        no allocation; one such sample makes a whole tile of every predicted pass NaN.  "error": scan the frame and raise ValueError naming the
+        affected passes before any forward launch.  "repair": scan, then replace every such value by the mean of the finite values of its channel
+        in the (2 nonfinite_radius + 1)^2 window, on the device and without a host synchronisation; nonfinite_report() gives the counts."""
+        if nonfinite not in ("keep", "error", "repair"):
+            raise ValueError('nonfinite must be "keep", "error" or "repair", not %r' % (nonfinite,))
+        if not 1 <= int(nonfinite_radius) <= 4:
+            raise ValueError("nonfinite_radius must be 1 .. 4, not %r" % (nonfinite_radius,))
+        self.nonfinite, self.nonfinite_radius = nonfinite, int(nonfinite_radius)
+        self._scanners, self._scanner = {}, None
         self.arch, self.tile_size, self.tile_overlap_size, self.tiles_per_batch = architecture, tile_size, tile_overlap_size, tiles_per_batch
         self.lib = L.load()
         self.use_graph = use_graph
@@ -93,6 +103,8 @@ class Predictor:
             fr = frame[Naming.source_feature_name(f.name, index=0)]
             if fr.dim() != 3 or fr.shape[2] < f.number_of_channels or tuple(fr.shape[:2]) != (H, W):
                 raise ValueError("%s: expected a [%d,%d,>=%d] frame, got %s" % (f.name, H, W, f.number_of_channels, tuple(fr.shape)))
+        if self.nonfinite != "keep":
+            self._scan_frame(features, frame, feats)
         flag_frames = {}
         for name, buf in prog.flags_raw.items():
             key = Naming.feature_flags_name(name)
@@ -146,6 +158,42 @@ class Predictor:
             ev[3].record()
             self.profile.append(ev)
         return out
+
+    def _scan_frame(self, features, frame, feats):
+        """nonfinite = "error" / "repair": the required source passes of the frame through nonfinite.Scanner, on the program's stream and in
+        front of the first tile batch, so the in-place input assembly and dd_extract_tiles both see repaired passes.  The caller's tensors are
+        never modified: a pass that IS the caller's tensor (already a contiguous fp32 device tensor) is cloned before it is repaired."""
+        from .nonfinite import Scanner
+        keys = list(dict.fromkeys(Naming.source_feature_name(f.name, index=0) for f in feats))
+        channels = {Naming.source_feature_name(f.name, index=0): f.number_of_channels for f in feats}
+        if self.nonfinite == "repair":
+            for k in keys:
+                if torch.is_tensor(features[k]) and features[k].data_ptr() == frame[k].data_ptr():
+                    frame[k] = frame[k].clone()
+        sig = tuple((k, tuple(frame[k].shape), channels[k]) for k in keys)
+        if sig not in self._scanners:
+            self._scanners[sig] = Scanner(self.arch.device, sig)
+        self._scanner = self._scanners[sig]
+        self._scanner.scan(frame)
+        if self.nonfinite == "repair":
+            self._scanner.repair(frame, radius=self.nonfinite_radius)
+            return
+        bad = {k: v for k, v in self._scanner.report().items() if v["values"]}
+        if bad:
+            raise ValueError("non-finite values in the frame: " + "; ".join("%s: %d values in %d pixels" % (k, v["values"], v["pixels"])
+                                                                             for k, v in bad.items()))
+
+    def nonfinite_report(self):
+        """{'source_image/0/<Pass>': {"values": int, "pixels": int}} of the last frame scanned (nonfinite = "error" / "repair"); synchronises."""
+        if self._scanner is None:
+            raise RuntimeError('nonfinite_report() needs a frame predicted with nonfinite="error" or "repair"')
+        return self._scanner.report()
+
+    def nonfinite_masks(self):
+        """{'source_image/0/<Pass>': uint8 [H,W] device plane, bit c set where channel c was non-finite} of the last frame scanned."""
+        if self._scanner is None:
+            raise RuntimeError('nonfinite_masks() needs a frame predicted with nonfinite="error" or "repair"')
+        return self._scanner.masks()
 
     def _forward(self, prog):
         """The tile program's forward launches, replayed from a hipGraph after one eager pass (the ~80 launches of a batch of tiles

@@ -572,6 +572,29 @@ typedef struct {
 } dd_recombine_desc;
 int dd_recombine(const dd_recombine_desc* desc, long npix, dd_stream stream);
 
+/* ---- NaN / Inf samples of render passes in device memory (csrc/dd_nonfinite.hip).  A table of up to DD_NONFINITE_MAX_PLANES planes that share
+ * N, H, W (a frame: N = 1; a batch of tiles: N > 1), all served by ONE launch.  A plane: fp32 data [N,H,W,ld] of which the first C (1 or 3)
+ * channels are looked at, ld >= C, and its uint8 mask [N,H,W].  "Non-finite" is a test on the bits -- all eight exponent bits set: +-inf,
+ * quiet and signalling NaNs of either sign; +-FLT_MAX, denormals and -0 are finite.  desc is a HOST struct (copied by value).  A bad argument
+ * (a NULL table or counts, n_planes outside 1 .. 32, C outside {1, 3}, ld < C, a NULL plane pointer, N H W beyond the 32-bit pixel index,
+ * radius outside 1 .. 4) returns a negative status without a launch.  No host sync. */
+#define DD_NONFINITE_MAX_PLANES 32
+typedef struct { float* data; int C; int ld; unsigned char* mask; } dd_nonfinite_plane;
+typedef struct { int n_planes; dd_nonfinite_plane plane[DD_NONFINITE_MAX_PLANES]; } dd_nonfinite_desc;
+/* What NaNHighlighter.py:40-42 computes per file on the host (255 * !isfinite per channel), for every plane of the table: mask byte of every
+ * pixel = bit c set when channel c is non-finite (zero bytes are written too: the mask needs no memset), and
+ * counts[2 * plane] += non-finite values, counts[2 * plane + 1] += pixels with at least one (DEVICE uint64 pairs, zeroed by the caller;
+ * integer atomics: exact, the same from run to run).  Every value is read once; a dense plane (ld == C, data 16-byte and mask 4-byte
+ * aligned) with 16-byte loads. */
+int dd_nonfinite_scan(const dd_nonfinite_desc* desc, int N, int H, int W, uint64_t* counts, dd_stream stream);
+/* Where OpenEXRDirectory.py:72-76 gives the frame up (it marks a directory with a non-finite value invalid), repair it IN PLACE after a
+ * dd_nonfinite_scan of the same table: every value whose mask bit is set becomes the mean of the values of the same channel and image in
+ * the (2 radius + 1)^2 window around it whose mask bit is clear -- the window clipped to the image, the values added in row-major window
+ * order in fp32 and divided once by their count; 0.0f when the window holds none.  Usable neighbours are decided from the mask planes alone;
+ * only masked positions are written and only unmasked ones read, so the result does not depend on scheduling.  Values that are not masked
+ * are never written.  The workgroups of a plane with counts[2 * plane + 1] == 0 return at once. */
+int dd_nonfinite_repair(const dd_nonfinite_desc* desc, int N, int H, int W, int radius, const uint64_t* counts, dd_stream stream);
+
 /* ---- small helpers of the graph executor */
 /* dst (+)= src * (mask > 0)   (identity/residual gradient paths into ReLU outputs); mask may be NULL */
 int dd_masked_add(void* dst, int lddst, const void* src, int ldsrc, const void* mask, int ldmask, int C, long npix,
