@@ -21,6 +21,7 @@ HISTOGRAM_VALUES_SCRATCH_BYTES = 20480
 PREVIEW_SOURCE, PREVIEW_PREDICTION, PREVIEW_TARGET, PREVIEW_DIFFERENCE = 1, 2, 4, 8
 PREVIEW_MAX_IMAGES, PREVIEW_THRESHOLDS = 16, 255
 NONFINITE_MAX_PLANES = 32      # DD_NONFINITE_MAX_PLANES
+QUALITY_MAX_PAIRS, QUALITY_TILE = 32, 32      # DD_QUALITY_MAX_PAIRS, DD_QUALITY_TILE
 
 
 def histogram_stats_offset(nb):
@@ -47,7 +48,7 @@ SYMBOLS = (
     "dd_loss_metrics_scratch_bytes", "dd_loss_metrics", "dd_loss_head_path_count",
     "dd_loss_head_dscale", "dd_loss_msssim_bwd_dscale", "dd_grads_nonfinite", "dd_adam_step_scaled", "dd_scaler_update",
     "dd_histogram_values", "dd_loss_histograms_scratch_bytes", "dd_loss_histograms", "dd_loss_previews",
-    "dd_nonfinite_scan", "dd_nonfinite_repair",
+    "dd_nonfinite_scan", "dd_nonfinite_repair", "dd_frame_quality_scratch_bytes", "dd_frame_quality",
 )
 
 
@@ -221,6 +222,16 @@ class NonfiniteDesc(C.Structure):       # dd_nonfinite_desc
     _fields_ = [("n_planes", C.c_int), ("plane", NonfinitePlane * NONFINITE_MAX_PLANES)]
 
 
+class QualityPair(C.Structure):         # dd_quality_pair
+    _fields_ = [("pred", C.c_void_p), ("target", C.c_void_p), ("pred_ld", C.c_int), ("target_ld", C.c_int), ("nch", C.c_int)]
+
+
+class QualityRecord(C.Structure):       # dd_quality_record: what dd_frame_quality leaves per pair in device memory (72 bytes)
+    _fields_ = [("pixels_valid", C.c_uint64), ("windows_valid", C.c_uint64), ("ldr_sq_err", C.c_uint64),
+                ("se", C.c_double), ("ae", C.c_double), ("rse", C.c_double), ("smape", C.c_double), ("ssim_sum", C.c_double),
+                ("max_abs", C.c_float), ("reserved", C.c_float)]
+
+
 _lib = None
 
 
@@ -323,6 +334,9 @@ def load():
     lib.dd_scaler_update.argtypes = [vp, f, f, i, f, f, vp]
     lib.dd_nonfinite_scan.argtypes = [C.POINTER(NonfiniteDesc), i, i, i, vp, vp]
     lib.dd_nonfinite_repair.argtypes = [C.POINTER(NonfiniteDesc), i, i, i, i, vp, vp]
+    lib.dd_frame_quality_scratch_bytes.argtypes = [i, i, i]
+    lib.dd_frame_quality_scratch_bytes.restype = C.c_long
+    lib.dd_frame_quality.argtypes = [C.POINTER(QualityPair), i, i, i, vp, f, f, C.POINTER(vp), vp, vp, vp]
     lib.dd_stitch.argtypes = [vp, i, i, vp, i, i, i, i, vp, i, vp]
     lib.dd_recombine.argtypes = [C.POINTER(RecombineDesc), l, vp]
     lib.dd_probe_tr16.argtypes = [vp, vp, vp, vp]

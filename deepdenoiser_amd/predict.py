@@ -32,7 +32,37 @@ def parser():
                    help="NaN / Inf samples in the input passes: keep them (a whole tile of the output turns NaN), stop with an error that names "
                         "the passes, or repair each from the finite values around it before denoising")
     p.add_argument("--nonfinite_png", action="store_true", help="write <Pass>_nonfinite.png next to the inputs for every pass with NaN / Inf samples")
+    p.add_argument("--target", type=str, default=None,
+                   help="directory with the ground-truth render of the frame (one .exr per pass): score every denoised pass and Combined against it on "
+                        "the device, print one line per pass and write quality.json")
+    p.add_argument("--exposure", type=float, default=1.0, help="--target: factor in front of the 8-bit sRGB quantisation of psnr_8bit and ssim")
+    p.add_argument("--quality_json", type=str, default=None, help="--target: where to write the figures (default: quality.json next to the inputs)")
+    p.add_argument("--ssim_png", action="store_true", help="--target: write <Pass>_ssim.png, the SSIM map (gray; magenta: a window with a NaN / Inf pixel)")
     return p
+
+
+def report_quality(args, arch, out):
+    """--target: the predictions `out` (still on the device) against the target frame: one dd_frame_quality call, one copy of the records."""
+    from . import quality      # (imported here: a run without --target does not load it)
+    targets = quality.targets_of_frame(args.target, arch, device=arch.device)
+    result = quality.FrameQuality(arch.device, exposure=args.exposure).measure(out, targets, ssim_maps=args.ssim_png)
+    maps = {}
+    if args.ssim_png:
+        result, maps = result
+    short = {(k.split("/", 1)[1] if k.startswith("prediction/") else k): v for k, v in result.items()}
+    for line in quality.table_lines(short):
+        print(line)
+    for key, ssim_map in maps.items():
+        path = os.path.join(args.input, (key.split("/", 1)[1] if key.startswith("prediction/") else key) + "_ssim.png")
+        with open(path, "wb") as f:
+            f.write(encode_png(quality.ssim_picture(ssim_map)))
+        print(path)
+    path = args.quality_json or os.path.join(args.input, "quality.json")
+    document = {"tile_size": int(args.tile_size), "tile_overlap_size": int(args.tile_overlap_size), "dtype": args.dtype, "nonfinite": args.nonfinite,
+                "exposure": float(args.exposure), "quality": result}
+    with open(path, "w") as f:
+        json.dump(document, f, indent=1)
+    print(path)
 
 
 def report_nonfinite(source, directory, write_png):
@@ -84,6 +114,8 @@ def main(args):
         report_nonfinite(scanner, args.input, True)
     for path in openexr.save_predictions(args.input, out, as_exr=args.exr):        # Prediction.py:483-510
         print(path)
+    if args.target:
+        report_quality(args, arch, out)
 
 
 if __name__ == "__main__":

@@ -18,6 +18,7 @@ from .tiling import tile_plan
 
 _COMBINED = ("Diffuse", "Glossy", "Subsurface", "Transmission")
 _SINGLES = ("Volume Direct", "Volume Indirect", "Environment", "Emission")
+RECOMBINE_MEMBERS = tuple(c + s for c in _COMBINED for s in (" Color", " Direct", " Indirect")) + _SINGLES      # every pass 'Combined' is formed from
 
 
 class Predictor:
@@ -214,19 +215,28 @@ class Predictor:
 
     def _recombine(self, prog, frames, out, npix, stream):
         idx = prog.head_index
-        need = [c + s for c in _COMBINED for s in (" Color", " Direct", " Indirect")] + list(_SINGLES)
-        if not all(n in idx and prog.head[idx[n]].load_data for n in need):
+        if not all(n in idx and prog.head[idx[n]].load_data for n in RECOMBINE_MEMBERS):
             return
-        comb = torch.zeros((len(_COMBINED) + 1,) + tuple(frames.shape[1:]), dtype=torch.float32, device=frames.device)
-        d = L.RecombineDesc()
-        d.n_triples = len(_COMBINED)
-        for k, c in enumerate(_COMBINED):
-            d.color[k], d.direct[k], d.indirect[k] = (frames[idx[c + s]].data_ptr() for s in (" Color", " Direct", " Indirect"))
-            d.combined[k] = comb[k].data_ptr()
-            out[Naming.feature_prediction_name(c)] = comb[k]
-        d.n_singles = len(_SINGLES)
-        for j, s in enumerate(_SINGLES):
-            d.single[j] = frames[idx[s]].data_ptr()
-        d.image = comb[len(_COMBINED)].data_ptr()
-        L.check(self.lib.dd_recombine(C.byref(d), npix, stream))
-        out["Combined"] = comb[len(_COMBINED)]
+        out.update(recombine(self.lib, {n: frames[idx[n]] for n in RECOMBINE_MEMBERS}, npix, stream))
+
+
+def recombine(lib, passes, npix, stream):
+    """The recombination of Prediction.py:443-481 by dd_recombine: passes = {pass name: contiguous fp32 [H,W,3] device tensor} with every name
+    of RECOMBINE_MEMBERS -> {'prediction/<combined feature>': [H,W,3]} for the four combined features, then 'Combined'.  Predictor._recombine
+    forms them from the predicted frames, quality.targets_of_frame from the target frames: one launch either way."""
+    first = passes[RECOMBINE_MEMBERS[0]]
+    comb = torch.zeros((len(_COMBINED) + 1,) + tuple(first.shape), dtype=torch.float32, device=first.device)
+    out = {}
+    d = L.RecombineDesc()
+    d.n_triples = len(_COMBINED)
+    for k, c in enumerate(_COMBINED):
+        d.color[k], d.direct[k], d.indirect[k] = (passes[c + s].data_ptr() for s in (" Color", " Direct", " Indirect"))
+        d.combined[k] = comb[k].data_ptr()
+        out[Naming.feature_prediction_name(c)] = comb[k]
+    d.n_singles = len(_SINGLES)
+    for j, s in enumerate(_SINGLES):
+        d.single[j] = passes[s].data_ptr()
+    d.image = comb[len(_COMBINED)].data_ptr()
+    L.check(lib.dd_recombine(C.byref(d), npix, stream))
+    out["Combined"] = comb[len(_COMBINED)]
+    return out

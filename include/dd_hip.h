@@ -595,6 +595,45 @@ int dd_nonfinite_scan(const dd_nonfinite_desc* desc, int N, int H, int W, uint64
  * are never written.  The workgroups of a plane with counts[2 * plane + 1] == 0 return at once. */
 int dd_nonfinite_repair(const dd_nonfinite_desc* desc, int N, int H, int W, int radius, const uint64_t* counts, dd_stream stream);
 
+/* ---- full-frame quality of a denoised frame against its target, where the frames are (csrc/dd_quality.hip).  Up to DD_QUALITY_MAX_PAIRS
+ * (prediction, target) pairs of one frame size in ONE call: one scoring launch over all pairs and one launch that adds the workgroups'
+ * partial records up.  A pair: two fp32 images [H,W,ld] of which the first nch (1 or 3) channels are used, ld >= nch (a 1-channel
+ * prediction is a [..., :1] view of a 3-wide frame: ld 3, nch 1).  pairs is a HOST array (copied by value).
+ *   valid pixel  : all nch channels of BOTH images finite (the bit test of dd_nonfinite_scan); an invalid pixel adds to nothing but is
+ *                  missing from pixels_valid.  valid window: all 121 pixels of an 11 x 11 window valid.
+ * A RECORD (DEVICE, 72 bytes, 8-byte aligned, overwritten):
+ *   uint64 pixels_valid, windows_valid     exact
+ *   uint64 ldr_sq_err                      sum over valid pixels and channels of (b_p - b_t)^2, the byte b of a channel = the number of entries
+ *                                          of `thresholds` <= exposure * value (one fp32 multiply; the rule and the table of dd_loss_previews,
+ *                                          metrics.preview_thresholds: the sRGB display value).  Exact.  PSNR_8bit = 10 log10(255^2 n / this)
+ *   double se, ae, rse, smape              scene-referred sums over valid pixels and channels of the fp32 terms (one rounding per operation)
+ *                                          (p-t)^2 | |p-t| | (p-t)^2 / (t^2 + epsilon) | |p-t| / (|p| + |t| + epsilon): the SQUARED, ABSOLUTE
+ *                                          and SMAPE forms of LossDifference.py:18-34 (epsilon: its 1e-2) and the relative MSE; `exposure`
+ *                                          never touches them
+ *   double ssim_sum                        sum over valid windows of the window's SSIM: on byte / 255, per channel the 11 x 11 Gaussian of
+ *                                          sigma 1.5 (normalised, VALID positions), C1 = 0.01^2, C2 = 0.03^2 (tf.image.ssim as the ms_ssim term
+ *                                          calls it, max_val 1: csrc/dd_loss_msssim.hip level 0),
+ *                                          (2 mx my + C1)(2 sxy + C2) / ((mx^2 + my^2 + C1)(sx^2 + sy^2 + C2)), then the mean over the channels
+ *   float max_abs; float reserved (0)      max over valid pixels and channels of the fp32 |p-t|
+ * ssim_maps: HOST array of n_pairs DEVICE pointers, or NULL; a non-NULL entry receives the pair's [(H-10),(W-10)] fp32 map, an invalid window
+ * as NaN: every element written exactly once and nothing else.  With H < 11 or W < 11 there are no windows: windows_valid = 0, ssim_sum = 0,
+ * the map pointer is ignored.  Window moments are accumulated in double from the integer bytes, every sum across a workgroup's pixels and
+ * across workgroups in double in a fixed order (no floating-point atomics): two runs give the same bits, and a pair's record depends neither
+ * on its index nor on the other pairs of the call.  A workgroup owns DD_QUALITY_TILE^2 pixels and the windows that start there.  scratch:
+ * >= dd_frame_quality_scratch_bytes (negative for a bad shape), 8-byte aligned.  A bad argument (n_pairs outside 1 .. 32, nch outside {1, 3},
+ * ld < nch, H or W < 1, a NULL pred / target / thresholds / records / scratch) returns a negative status without a launch.  No host sync. */
+#define DD_QUALITY_MAX_PAIRS 32
+#define DD_QUALITY_TILE 32
+typedef struct { const float* pred; const float* target; int pred_ld, target_ld, nch; } dd_quality_pair;
+typedef struct {
+  uint64_t pixels_valid, windows_valid, ldr_sq_err;
+  double se, ae, rse, smape, ssim_sum;
+  float max_abs, reserved;
+} dd_quality_record;
+long dd_frame_quality_scratch_bytes(int n_pairs, int H, int W);
+int dd_frame_quality(const dd_quality_pair* pairs, int n_pairs, int H, int W, const float* thresholds, float exposure, float epsilon,
+                     float* const* ssim_maps, void* records, void* scratch, dd_stream stream);
+
 /* ---- small helpers of the graph executor */
 /* dst (+)= src * (mask > 0)   (identity/residual gradient paths into ReLU outputs); mask may be NULL */
 int dd_masked_add(void* dst, int lddst, const void* src, int ldsrc, const void* mask, int ldmask, int C, long npix,
