@@ -48,7 +48,7 @@ SYMBOLS = (
     "dd_loss_metrics_scratch_bytes", "dd_loss_metrics", "dd_loss_head_path_count",
     "dd_loss_head_dscale", "dd_loss_msssim_bwd_dscale", "dd_grads_nonfinite", "dd_adam_step_scaled", "dd_scaler_update",
     "dd_histogram_values", "dd_loss_histograms_scratch_bytes", "dd_loss_histograms", "dd_loss_previews",
-    "dd_nonfinite_scan", "dd_nonfinite_repair", "dd_frame_quality_scratch_bytes", "dd_frame_quality",
+    "dd_nonfinite_scan", "dd_nonfinite_repair", "dd_frame_quality_scratch_bytes", "dd_frame_quality", "dd_stitch_blend",
 )
 
 
@@ -178,6 +178,11 @@ AUG_PLAIN, AUG_RGB, AUG_NORMAL, AUG_SCREEN_NORMAL = 0, 1, 2, 3
 class StitchEntry(C.Structure):
     _fields_ = [("tile", C.c_int), ("crop_y0", C.c_int), ("crop_y1", C.c_int), ("crop_x0", C.c_int),
                 ("crop_x1", C.c_int), ("dst_img", C.c_int), ("dst_y", C.c_int), ("dst_x", C.c_int)]
+
+
+class BlendAxis(C.Structure):          # dd_blend_axis: `origins` is a host array, the other tables are device memory
+    _fields_ = [("count", C.c_int), ("origins", C.POINTER(C.c_int)), ("origins_dev", C.c_void_p), ("weights", C.c_void_p),
+                ("first", C.c_void_p), ("last", C.c_void_p)]
 
 
 class ComposeArgs(C.Structure):
@@ -338,6 +343,7 @@ def load():
     lib.dd_frame_quality_scratch_bytes.restype = C.c_long
     lib.dd_frame_quality.argtypes = [C.POINTER(QualityPair), i, i, i, vp, f, f, C.POINTER(vp), vp, vp, vp]
     lib.dd_stitch.argtypes = [vp, i, i, vp, i, i, i, i, vp, i, vp]
+    lib.dd_stitch_blend.argtypes = [vp, i, i, i, vp, i, i, i, i, i, C.POINTER(BlendAxis), C.POINTER(BlendAxis), i, i, vp]
     lib.dd_recombine.argtypes = [C.POINTER(RecombineDesc), l, vp]
     lib.dd_probe_tr16.argtypes = [vp, vp, vp, vp]
     lib.dd_masked_add.argtypes = [vp, i, vp, i, vp, i, i, l, i, i, vp]

@@ -27,7 +27,7 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-u
 NO_SCRATCH = {
     "dd_conv_bwd.hip": ("conv_bwd_kernel", "conv_bwd_multi_kernel"),
     "dd_conv_bwd96.hip": ("conv_bwd96_kernel",),
-    "dd_pointwise.hip": ("kpcn_fwd_kernel", "kpcn_bwd_kernel", "assemble_input_kernel"),
+    "dd_pointwise.hip": ("kpcn_fwd_kernel", "kpcn_bwd_kernel", "assemble_input_kernel", "stitch_blend_kernel"),
     "dd_convt.hip": ("convt_bwd_kernel", "convt_fwd_kernel"),
     "dd_conv_rw.hip": ("conv_rw_kernel", "conv_rw8_kernel"),
     "dd_compose.hip": ("compose_fwd_kernel", "compose_bwd_kernel"),

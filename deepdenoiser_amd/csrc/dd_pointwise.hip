@@ -1788,6 +1788,78 @@ extern "C" int dd_stitch(const float* tiles, int tile_size, int ldt, float* fram
   return DD_OK;
 }
 
+// Feathered stitch, gather form: one thread owns one float of one frame row and walks the tiles that cover its pixel in ascending
+// row-major tile index -- tile rows first[y] .. last[y] (the same for the whole workgroup: scalar loads) times tile columns first[x] .. last[x]
+// -- adding w_y * w_x * tile value for the tiles of this launch, [first_tile, first_tile + n_tiles).  The sum starts from the stored value when
+// a covering tile lies below first_tile (an earlier launch has written this float) and from 0 otherwise, and is written once: no atomics, no
+// memset, and the same chain of roundings however the tiles are split into launches.  A float none of the launch's tiles covers is not touched.
+struct BlendAxis { const int* origins; const float* weights; const int* first; const int* last; int count; };
+template <int C>
+__global__ void __launch_bounds__(256) stitch_blend_kernel(const float* __restrict__ tiles, int ts, int ldt, int tiles_per_image, float* frames, int fh,
+                                                           int fw, int ldf, BlendAxis ry, BlendAxis rx, int y0, int first_tile, int n_tiles) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= fw * C) return;
+  const int y = y0 + blockIdx.y, x = i / C, c = i - x * C;
+  // (the host checked the origins; the cover tables are device memory it cannot see: a table that does not fit them reads no tile)
+  const int fy = max(ry.first[y], 0), ly = min(ry.last[y], ry.count - 1), fx = max(rx.first[x], 0), lx = min(rx.last[x], rx.count - 1);
+  float* dst = frames + (((long)blockIdx.z * fh + y) * fw + x) * ldf + c;
+  const float* src = tiles + (long)blockIdx.z * tiles_per_image * ts * ts * ldt + c;
+  const bool earlier = fy * rx.count + fx < first_tile;
+  bool mine = false;
+  float acc = 0.f;
+  for (int iy = fy; iy <= ly; ++iy) {
+    const int ty = y - ry.origins[iy];
+    if (ty < 0 || ty >= ts) continue;
+    const float wy = ry.weights[iy * ts + ty];
+    for (int ix = fx; ix <= lx; ++ix) {
+      const int slot = iy * rx.count + ix - first_tile, tx = x - rx.origins[ix];
+      if (slot < 0 || slot >= n_tiles || tx < 0 || tx >= ts) continue;
+      if (!mine) {
+        mine = true;
+        if (earlier) acc = *dst;
+      }
+      acc = fmaf(__fmul_rn(wy, rx.weights[ix * ts + tx]), src[(((long)slot * ts + ty) * ts + tx) * ldt], acc);
+    }
+  }
+  if (mine) *dst = acc;
+}
+static int blend_axis_ok(const dd_blend_axis* a, int tile, int extent) {
+  if (!a || a->count <= 0 || !a->origins || !a->origins_dev || !a->weights || !a->first || !a->last) return 0;
+  for (int i = 0; i < a->count; ++i)
+    if (a->origins[i] < 0 || a->origins[i] + tile > extent || (i && a->origins[i] < a->origins[i - 1])) return 0;
+  return 1;
+}
+extern "C" int dd_stitch_blend(const float* tiles, int tile_size, int ldt, int tiles_per_image, float* frames, int n_img, int frame_h, int frame_w,
+                               int ldf, int C, const dd_blend_axis* rows, const dd_blend_axis* cols, int first_tile, int n_tiles, dd_stream stream) {
+  DD_REQUIRE(tiles && frames && n_img > 0 && n_img <= 65535, "dd_stitch_blend: null tiles or frames, or %d images", n_img);
+  DD_REQUIRE(C >= 1 && C <= 4 && ldt >= C && ldf >= C, "dd_stitch_blend: C = %d channels (1 .. 4) with ldt = %d, ldf = %d", C, ldt, ldf);
+  DD_REQUIRE(tile_size > 0 && tile_size <= frame_h && tile_size <= frame_w && (long)frame_w * C <= 0x7fffffffL,
+             "dd_stitch_blend: tile %d does not fit the %dx%d frame", tile_size, frame_h, frame_w);
+  DD_REQUIRE(blend_axis_ok(rows, tile_size, frame_h) && blend_axis_ok(cols, tile_size, frame_w),
+             "dd_stitch_blend: an axis with a null table, or origins that leave the frame or do not ascend");
+  DD_REQUIRE(first_tile >= 0 && n_tiles > 0 && n_tiles <= tiles_per_image && (long)first_tile + n_tiles <= (long)rows->count * cols->count,
+             "dd_stitch_blend: tiles [%d, %d + %d) of %d x %d, %d tiles per image", first_tile, first_tile, n_tiles, rows->count, cols->count,
+             tiles_per_image);
+  // row-major tiles: the launch touches one contiguous band of frame rows
+  const int y0 = rows->origins[first_tile / cols->count], y1 = rows->origins[(first_tile + n_tiles - 1) / cols->count] + tile_size;
+  DD_REQUIRE(y1 - y0 <= 65535, "dd_stitch_blend: a band of %d rows", y1 - y0);
+  const BlendAxis ry{rows->origins_dev, rows->weights, rows->first, rows->last, rows->count};
+  const BlendAxis rx{cols->origins_dev, cols->weights, cols->first, cols->last, cols->count};
+  const dim3 grid((unsigned)((frame_w * C + 255) / 256), (unsigned)(y1 - y0), (unsigned)n_img);
+#define DD_BLEND_LAUNCH(CH)                                                                                                                    \
+  hipLaunchKernelGGL(stitch_blend_kernel<CH>, grid, dim3(256), 0, S(stream), tiles, tile_size, ldt, tiles_per_image, frames, frame_h, frame_w, \
+                     ldf, ry, rx, y0, first_tile, n_tiles)
+  switch (C) {
+    case 1: DD_BLEND_LAUNCH(1); break;
+    case 2: DD_BLEND_LAUNCH(2); break;
+    case 3: DD_BLEND_LAUNCH(3); break;
+    default: DD_BLEND_LAUNCH(4); break;
+  }
+#undef DD_BLEND_LAUNCH
+  DD_LAUNCH_CHECK();
+  return DD_OK;
+}
+
 // One workgroup row = one tile row: threads walk the T*C contiguous floats of the row (float4 when both sides allow it).
 __global__ void extract_tiles_kernel(const float* __restrict__ frame, int fw, int ldf, int C, float* __restrict__ tiles, int ts, int ldt,
                                      const int* __restrict__ origins) {

@@ -32,6 +32,12 @@ def parser():
                    help="NaN / Inf samples in the input passes: keep them (a whole tile of the output turns NaN), stop with an error that names "
                         "the passes, or repair each from the finite values around it before denoising")
     p.add_argument("--nonfinite_png", action="store_true", help="write <Pass>_nonfinite.png next to the inputs for every pass with NaN / Inf samples")
+    p.add_argument("--tile_blend", default="crop", choices=["crop", "feather"],
+                   help="how overlapping tiles become the frame: crop keeps one tile's prediction per pixel (the reference's stitch), feather blends "
+                        "every tile that covers a pixel with weights that ramp across the overlap, which removes the step along tile borders")
+    p.add_argument("--blend_width", type=int, default=None,
+                   help="--tile_blend feather: pixels over which a tile's weight ramps at a side that faces another tile (default: twice the overlap; "
+                        "0: plain average; at most half a tile)")
     p.add_argument("--target", type=str, default=None,
                    help="directory with the ground-truth render of the frame (one .exr per pass): score every denoised pass and Combined against it on "
                         "the device, print one line per pass and write quality.json")
@@ -59,7 +65,7 @@ def report_quality(args, arch, out):
         print(path)
     path = args.quality_json or os.path.join(args.input, "quality.json")
     document = {"tile_size": int(args.tile_size), "tile_overlap_size": int(args.tile_overlap_size), "dtype": args.dtype, "nonfinite": args.nonfinite,
-                "exposure": float(args.exposure), "quality": result}
+                "tile_blend": args.tile_blend, "exposure": float(args.exposure), "quality": result}
     with open(path, "w") as f:
         json.dump(document, f, indent=1)
     print(path)
@@ -90,7 +96,7 @@ def main(args):
     height, width = first.shape[0], first.shape[1]
     mode = args.nonfinite
     predictor = Predictor(arch, tile_size=int(args.tile_size), tile_overlap_size=int(args.tile_overlap_size), tiles_per_batch=args.tiles_per_batch,
-                          nonfinite=mode)
+                          nonfinite=mode, tile_blend=args.tile_blend, blend_width=args.blend_width)
     predictor.prepare(height, width)                                               # raises for frames smaller than 16 pixels (Prediction.py:259-261)
     directory = os.path.dirname(os.path.abspath(args.json_filename))
     model_dir = aj["model_directory"] if os.path.isabs(aj["model_directory"]) else os.path.join(directory, aj["model_directory"])

@@ -4,7 +4,8 @@ Mirrors the reference's Prediction.main (TensorFlow/Prediction.py:188-520) for t
 the integer tile plan and crop windows (bit-exact, tiling.py), row-major tile order (:325-326, :380-382), stitch
 (:384-441) and recombination (:443-481).  Differences by design: tiles are batched
 (the reference's batch-1 Estimator.predict and its temporary TFRecord round trip, :316-338, are not part of the
-contract), and crop/stitch/recombine run on the device.  EXR decode (cv2) is out of scope: frames are given as
+contract), crop/stitch/recombine run on the device, and tile_blend="feather" blends the overlapping tile predictions instead of cropping them
+(dd_stitch_blend; the default "crop" is the reference's stitch).  EXR decode (cv2) is out of scope: frames are given as
 tensors keyed by the reference's feature names.
 """
 import ctypes as C
@@ -14,16 +15,45 @@ import torch
 
 from . import _lib as L
 from .naming import Naming
-from .tiling import tile_plan
+from .tiling import blend_cover, blend_weights, tile_plan
 
 _COMBINED = ("Diffuse", "Glossy", "Subsurface", "Transmission")
 _SINGLES = ("Volume Direct", "Volume Indirect", "Environment", "Emission")
 RECOMBINE_MEMBERS = tuple(c + s for c in _COMBINED for s in (" Color", " Direct", " Indirect")) + _SINGLES      # every pass 'Combined' is formed from
 
 
+class BlendTables:
+    """What dd_stitch_blend needs of a tile plan: per axis the origins, the normalised weights of tiling.blend_weights and the first / last
+    covering tile of every image coordinate, on the device, and the two dd_blend_axis structs that point at them."""
+
+    def __init__(self, plan, device, width=None):
+        self.plan, self._keep = plan, []
+        self.rows, self.cols = self._axis(plan.rows, device, width), self._axis(plan.cols, device, width)
+
+    def _axis(self, axis, device, width):
+        first, last = blend_cover(axis)
+        host = (C.c_int * axis.count)(*axis.origins)
+        dev = [torch.tensor(axis.origins, dtype=torch.int32, device=device), torch.from_numpy(blend_weights(axis, width)).to(device).contiguous(),
+               torch.tensor(first, dtype=torch.int32, device=device), torch.tensor(last, dtype=torch.int32, device=device)]
+        self._keep += [host] + dev
+        return L.BlendAxis(axis.count, host, *(t.data_ptr() for t in dev))
+
+    def blend(self, lib, tiles_ptr, ldt, tiles_per_image, frames, C_, first_tile, n_tiles, stream):
+        """frames [n_img, H, W, ldf] += the tiles [first_tile, first_tile + n_tiles) of the plan, read from [n_img * tiles_per_image, T, T, ldt]."""
+        if tuple(frames.shape[1:3]) != (self.plan.height, self.plan.width):      # (the cover tables are as long as the plan's frame is large)
+            raise ValueError("frames of %dx%d for the tables of a %dx%d plan" % (frames.shape[1], frames.shape[2], self.plan.height, self.plan.width))
+        L.check(lib.dd_stitch_blend(tiles_ptr, self.plan.tile, ldt, tiles_per_image, frames.data_ptr(), frames.shape[0], frames.shape[1],
+                                    frames.shape[2], frames.shape[3], C_, C.byref(self.rows), C.byref(self.cols), first_tile, n_tiles, stream))
+
+
 class Predictor:
-    def __init__(self, architecture, tile_size=128, tile_overlap_size=14, tiles_per_batch=16, use_graph=True, nonfinite="keep", nonfinite_radius=2):
-        """nonfinite: what to do about NaN / Inf samples in the source passes of a frame (nonfinite.py).  "keep": nothing -- no scan, no launch,
+    def __init__(self, architecture, tile_size=128, tile_overlap_size=14, tiles_per_batch=16, use_graph=True, nonfinite="keep", nonfinite_radius=2,
+                 tile_blend="crop", blend_width=None):
+        """tile_blend: how the overlapping tile predictions become the frame.  "crop": one tile's prediction per pixel, the others dropped
+        (Prediction.py:384-441, bit for bit).  "feather": every pixel is the weighted mean of all tiles that cover it, the weights ramping
+        linearly over blend_width pixels at every tile side that faces another tile (tiling.blend_weights; None: twice the plan's
+        overlap), by dd_stitch_blend next to the forward -- no step along the tile borders; the output does not depend on tiles_per_batch.
+        nonfinite: what to do about NaN / Inf samples in the source passes of a frame (nonfinite.py).  "keep": nothing -- no scan, no launch,
         no allocation; one such sample makes a whole tile of every predicted pass NaN.  "error": scan the frame and raise ValueError naming the
         affected passes before any forward launch.  "repair": scan, then replace every such value by the mean of the finite values of its channel
         in the (2 nonfinite_radius + 1)^2 window, on the device and without a host synchronisation; nonfinite_report() gives the counts."""
@@ -31,12 +61,17 @@ class Predictor:
             raise ValueError('nonfinite must be "keep", "error" or "repair", not %r' % (nonfinite,))
         if not 1 <= int(nonfinite_radius) <= 4:
             raise ValueError("nonfinite_radius must be 1 .. 4, not %r" % (nonfinite_radius,))
+        if tile_blend not in ("crop", "feather"):
+            raise ValueError('tile_blend must be "crop" or "feather", not %r' % (tile_blend,))
+        if blend_width is not None and not 0 <= int(blend_width) <= int(tile_size) // 2:
+            raise ValueError("blend_width must be 0 .. tile_size // 2 = %d, not %r" % (int(tile_size) // 2, blend_width))
+        self.tile_blend, self.blend_width = tile_blend, None if blend_width is None else int(blend_width)
         self.nonfinite, self.nonfinite_radius = nonfinite, int(nonfinite_radius)
         self._scanners, self._scanner = {}, None
         self.arch, self.tile_size, self.tile_overlap_size, self.tiles_per_batch = architecture, tile_size, tile_overlap_size, tiles_per_batch
         self.lib = L.load()
         self.use_graph = use_graph
-        self._plans, self._graphs = {}, {}
+        self._plans, self._graphs, self._blends = {}, {}, {}
         self.profile = None          # a list: predict_frame appends (start, before forward, after forward, end) timing events per tile batch / frame
 
     def prepare(self, H, W):
@@ -79,6 +114,8 @@ class Predictor:
                     n += 1
             tdev = torch.frombuffer(bytearray(bytes(table)), dtype=torch.uint8).to(dev)
             chunks.append((oyx, tdev, n))
+        if self.tile_blend == "feather":      # (raises for a blend_width beyond half of the tile a small frame shrank the plan to)
+            self._blends[key] = BlendTables(plan, dev, self.blend_width)
         self._plans[key] = (plan, prog, chunks)
         return self._plans[key]
 
@@ -131,6 +168,7 @@ class Predictor:
         if self.profile is not None:      # (bench.py: where a frame's time goes on the device, and how long the device waits for the host between frames)
             ev = [torch.cuda.Event(enable_timing=True) for _ in range(4)]
             ev[0].record()
+        blend, first_tile = self._blends.get((H, W)), 0
         for oyx, tdev, n in chunks:
             if direct:
                 prog.frame_origins.copy_(oyx, non_blocking=True)
@@ -149,7 +187,11 @@ class Predictor:
             if ev is not None and oyx is chunks[-1][0]:
                 ev[2].record()
             tiles = prog.predictions[0]                                  # [NF*Bt, T, T, 3], feature-major
-            L.check(lib.dd_stitch(tiles.ptr, T, 3, frames.data_ptr(), H, W, 3, 3, tdev.data_ptr(), n, stream))
+            if blend is None:
+                L.check(lib.dd_stitch(tiles.ptr, T, 3, frames.data_ptr(), H, W, 3, 3, tdev.data_ptr(), n, stream))
+            else:                                                        # (n // NF: the batch's real tiles; a ragged batch's repeated tile is not one)
+                blend.blend(lib, tiles.ptr, 3, oyx.shape[0], frames, 3, first_tile, n // NF, stream)
+                first_tile += n // NF
         out = {}
         for f in arch.feature_predictions:
             if f.is_target and f.load_data:

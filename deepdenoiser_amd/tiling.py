@@ -89,6 +89,52 @@ def tile_plan(height, width, tile_size=128, tile_overlap_size=14) -> TilePlan:
     return TilePlan(height, width, tile, overlap, _axis(height, tile, overlap), _axis(width, tile, overlap))
 
 
+def blend_cover(axis: AxisPlan):
+    """Per image coordinate of the axis: (first, last) index of the tiles whose interval [origin, origin + tile) contains it, as two lists.
+    The origins ascend, so the covering tiles of a coordinate are exactly first .. last."""
+    first, last = [axis.count] * axis.extent, [-1] * axis.extent
+    for i, o in enumerate(axis.origins):
+        if i and o < axis.origins[i - 1]:
+            raise ValueError("tile origins %r do not ascend" % (axis.origins,))
+        for p in range(max(o, 0), min(o + axis.tile, axis.extent)):
+            first[p], last[p] = min(first[p], i), max(last[p], i)
+    if any(b < 0 for b in last):
+        raise ValueError("the tiles of the plan (tile %d, overlap %d) do not cover the extent %d" % (axis.tile, axis.overlap, axis.extent))
+    return first, last
+
+
+def blend_weights(axis: AxisPlan, width=None):
+    """tile_blend="feather" (not in the reference, which crops: Prediction.py:384-441): the normalised weight of every tile
+    of the axis at every tile coordinate, float32 [count, tile].
+
+    Raw weight of tile i at tile coordinate t: min(lo, hi) with lo = min(1, (t + 0.5) / width), or 1 for the tile at the low frame border
+    (origin 0), and hi = min(1, (tile - t - 0.5) / width), or 1 for the tile at the high border (origin + tile == extent): a linear ramp
+    over `width` pixels on every side that faces another tile.  width == 0: 1 everywhere (a plain average in the overlaps).  The
+    normalised weight is the raw weight over the sum of the raw weights of ALL tiles that cover the image coordinate (the last tile sits
+    at extent - tile and may overlap two predecessors); float64 throughout, rounded once.  A coordinate one tile covers has exactly 1.0.
+    width None: 2 * axis.overlap, what two neighbouring tiles share; any other width must be 0 .. tile // 2."""
+    import numpy as np
+    if width is None:
+        width = 2 * axis.overlap
+    elif not 0 <= width <= axis.tile // 2:
+        raise ValueError("blend width must be 0 .. tile // 2 = %d, not %r" % (axis.tile // 2, width))
+    T = axis.tile
+    t = np.arange(T, dtype=np.float64)
+    raw = np.ones((axis.count, T), dtype=np.float64)
+    if width > 0:
+        for i, o in enumerate(axis.origins):
+            lo = np.ones(T) if o == 0 else np.minimum(1.0, (t + 0.5) / width)
+            hi = np.ones(T) if o + T == axis.extent else np.minimum(1.0, (T - t - 0.5) / width)
+            raw[i] = np.minimum(lo, hi)
+    total = np.zeros(axis.extent, dtype=np.float64)
+    for i, o in enumerate(axis.origins):
+        total[o:o + T] += raw[i]
+    out = np.empty((axis.count, T), dtype=np.float64)
+    for i, o in enumerate(axis.origins):
+        out[i] = raw[i] / total[o:o + T]
+    return out.astype(np.float32)
+
+
 def training_tile_grid(height, width, tiles_height_width):
     """Training-side tiling of a rendered frame (TFRecordsCreator.py:125-133): non-overlapping tiles, remainders dropped.
     Returns (rows, cols, [(y0, y1, x0, x1), ...]) in the reference's loop order (row-major; its "x" indexes height)."""

@@ -557,6 +557,23 @@ typedef struct { int tile; int crop_y0, crop_y1, crop_x0, crop_x1; int dst_img, 
 int dd_stitch(const float* tiles, int tile_size, int ldt, float* frames, int frame_h, int frame_w, int ldf, int C,
               const dd_stitch_entry* table, int n_entries, dd_stream stream);
 
+/* ---- feathered stitch: the overlapping tile predictions blended instead of cropped.  A DEPARTURE from Prediction.py:384-441, which keeps one
+ * tile's prediction per output pixel and drops the others: neighbouring tiles see different context and disagree inside their overlap, and
+ * the crop turns that disagreement into a step along every tile border.  Here
+ *   frames[f][y][x][c] = sum over the tiles (i, j) that cover (y, x), ascending row-major index i * cols->count + j, of
+ *                        rows->weights[i][y - oy_i] * cols->weights[j][x - ox_j] * tiles[f * tiles_per_image + (i * cols->count + j - first_tile)][y - oy_i][x - ox_j][c]
+ * with normalised per-axis weights (deepdenoiser_amd/tiling.py blend_weights: they add up to 1 over the covering tiles of a coordinate), each
+ * term as fmaf(w_y * w_x, value, sum) in fp32.  One call adds the tiles [first_tile, first_tile + n_tiles) of a row-major plan; the tiles of a
+ * frame are given in ascending order over one or more calls on one stream.  A float starts from its stored value when a tile below first_tile
+ * covers it and from 0 otherwise, is written once per call by the one thread that owns it, and is not touched when none of the call's tiles
+ * covers it: frames need no memset, there are no atomics, and the result is bit-identical for every split of the tiles into calls.
+ * An axis (a HOST struct; `origins` a host array, the other tables device memory): count tiles of tile_size, ascending origins inside the
+ * frame; weights [count][tile_size]; first / last [extent]: the lowest and highest tile index that covers each image coordinate.
+ * tiles [n_img * tiles_per_image, tile_size, tile_size, ldt], frames [n_img, frame_h, frame_w, ldf], 1 <= C <= 4, ldt >= C, ldf >= C. */
+typedef struct { int count; const int* origins; const int* origins_dev; const float* weights; const int* first; const int* last; } dd_blend_axis;
+int dd_stitch_blend(const float* tiles, int tile_size, int ldt, int tiles_per_image, float* frames, int n_img, int frame_h, int frame_w, int ldf,
+                    int C, const dd_blend_axis* rows, const dd_blend_axis* cols, int first_tile, int n_tiles, dd_stream stream);
+
 /* ---- inference tile extraction (Prediction.py:283-310: tiled_feature = feature[lower_h:upper_h, lower_w:upper_w] for every window
  * of the plan): tiles[i] = frame[origin_y[i] : +tile_size, origin_x[i] : +tile_size, 0:C].  frame [frame_h, frame_w, ldf],
  * tiles [n_tiles, tile_size, tile_size, ldt] fp32; origins: n_tiles (y, x) int pairs on the device. */
