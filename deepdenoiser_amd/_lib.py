@@ -22,6 +22,7 @@ PREVIEW_SOURCE, PREVIEW_PREDICTION, PREVIEW_TARGET, PREVIEW_DIFFERENCE = 1, 2, 4
 PREVIEW_MAX_IMAGES, PREVIEW_THRESHOLDS = 16, 255
 NONFINITE_MAX_PLANES = 32      # DD_NONFINITE_MAX_PLANES
 QUALITY_MAX_PAIRS, QUALITY_TILE = 32, 32      # DD_QUALITY_MAX_PAIRS, DD_QUALITY_TILE
+GRAD_CHUNK, GRAD_PARTIAL_BYTES = 4096, 24      # DD_GRAD_CHUNK, DD_GRAD_PARTIAL_BYTES
 
 
 def histogram_stats_offset(nb):
@@ -49,6 +50,7 @@ SYMBOLS = (
     "dd_loss_head_dscale", "dd_loss_msssim_bwd_dscale", "dd_grads_nonfinite", "dd_adam_step_scaled", "dd_scaler_update",
     "dd_histogram_values", "dd_loss_histograms_scratch_bytes", "dd_loss_histograms", "dd_loss_previews",
     "dd_nonfinite_scan", "dd_nonfinite_repair", "dd_frame_quality_scratch_bytes", "dd_frame_quality", "dd_stitch_blend",
+    "dd_grad_norms", "dd_adam_step_clipped", "dd_adam_step_scaled_clipped",
 )
 
 
@@ -166,6 +168,19 @@ class ScalerState(C.Structure):
     """dd_scaler_state (include/dd_hip.h): the device-resident record of the dynamic loss scale.  Five 4-byte words; `scale` is the first, so a
     pointer to the record is a pointer to the scale (what the *_dscale loss launches take)."""
     _fields_ = [("scale", C.c_float), ("good_steps", C.c_int), ("found_nonfinite", C.c_int), ("adam_t", C.c_int), ("skipped_total", C.c_int)]
+
+
+class GradChunk(C.Structure):          # dd_grad_chunk: one row of the chunk table of dd_grad_norms (16 bytes)
+    _fields_ = [("offset", C.c_long), ("length", C.c_int), ("variable", C.c_int)]
+
+
+class GradVarNorms(C.Structure):       # dd_grad_var_norms: what dd_grad_norms leaves per variable in device memory (24 bytes)
+    _fields_ = [("grad_sq", C.c_double), ("weight_sq", C.c_double), ("nonfinite", C.c_uint), ("reserved", C.c_uint)]
+
+
+class GradClip(C.Structure):           # dd_grad_clip: the clip record of dd_grad_norms, read by the *_clipped Adam launches (five 4-byte words)
+    _fields_ = [("grad_norm", C.c_float), ("coef", C.c_float), ("grad_factor", C.c_float), ("nonfinite_variables", C.c_uint),
+                ("nonfinite_total", C.c_uint)]
 
 
 class AugmentDraw(C.Structure):
@@ -337,6 +352,9 @@ def load():
     lib.dd_grads_nonfinite.argtypes = [vp, l, vp, vp]
     lib.dd_adam_step_scaled.argtypes = [vp, vp, vp, vp, l, C.c_double, C.c_double, C.c_double, f, f, vp, vp]
     lib.dd_scaler_update.argtypes = [vp, f, f, i, f, f, vp]
+    lib.dd_grad_norms.argtypes = [vp, vp, vp, i, vp, i, vp, vp, vp, f, f, vp, vp]
+    lib.dd_adam_step_clipped.argtypes = [vp, vp, vp, vp, l, f, f, f, f, f, vp, vp]
+    lib.dd_adam_step_scaled_clipped.argtypes = [vp, vp, vp, vp, l, C.c_double, C.c_double, C.c_double, f, f, vp, vp, vp]
     lib.dd_nonfinite_scan.argtypes = [C.POINTER(NonfiniteDesc), i, i, i, vp, vp]
     lib.dd_nonfinite_repair.argtypes = [C.POINTER(NonfiniteDesc), i, i, i, i, vp, vp]
     lib.dd_frame_quality_scratch_bytes.argtypes = [i, i, i]

@@ -74,7 +74,7 @@ class FeaturePredictionTuple:
 
 class Architecture:
     def __init__(self, parsed_json, source_data_format="channels_last", data_format="channels_last",
-                 device="cuda", dtype="f32", seed=2, loss_scale=None):
+                 device="cuda", dtype="f32", seed=2, loss_scale=None, clip_norm=None, track_gradient_norms=False):
         # `data_format` is accepted for drop-in compatibility; the MI355X path is NHWC-native, both values give the same results.
         if source_data_format != "channels_last":
             raise ValueError("features are exchanged channels_last (NHWC), as in the reference's callers")
@@ -85,6 +85,10 @@ class Architecture:
         LS.parse(loss_scale, dtype)           # (refuses anything that is not None, a number, "dynamic" or a dict of dynamic settings)
         self.loss_scale = loss_scale          # None: the storage type's default (program.Program); "dynamic" / a dict: loss_scale.py
         self.loss_scaler = None               # the device-resident scaler of the dynamic mode, created with the first training program
+        from . import grad_clip as GC
+        self.clip_norm = GC.parse(clip_norm)  # None: no clipping; a positive finite number: tf.clip_by_global_norm's clip_norm (grad_clip.py)
+        self.track_gradient_norms = bool(track_gradient_norms)      # measure the gradient / weight norms of every step even without clipping
+        self.grad_clipper = None              # the device tables of either, created with the first training program
         self.model_directory = parsed_json["model_directory"]
         self.number_of_sources_per_target = parsed_json["number_of_sources_per_target"]
         if self.number_of_sources_per_target != 1:

@@ -109,10 +109,17 @@ class LossScaler:
     def skipped_steps(self):
         return self.state()["skipped_total"]
 
-    def step(self, ps, lr, grad_scale, beta1, beta2, eps, stream):
-        """Scan -> guarded Adam -> record update on `stream`, over the flat arenas of the ParamStore `ps`."""
+    def step(self, ps, lr, grad_scale, beta1, beta2, eps, stream, clipper=None):
+        """Scan -> guarded Adam -> record update on `stream`, over the flat arenas of the ParamStore `ps`.  With a grad_clip.GradientClipper its
+        two reduction launches run between the scan and the Adam launch (they divide by the scale the update is about to change), and the
+        Adam launch multiplies by the coefficient they left on the device."""
         lib, n, c = self.lib, ps.values.numel(), self.config
         L.check(lib.dd_grads_nonfinite(ps.grads.data_ptr(), n, self.ptr, stream))
-        L.check(lib.dd_adam_step_scaled(ps.values.data_ptr(), ps.grads.data_ptr(), ps.m.data_ptr(), ps.v.data_ptr(), n, lr, beta1, beta2, eps,
-                                        grad_scale, self.ptr, stream))
+        if clipper is not None:
+            clipper.measure(grad_scale, stream, scaler_ptr=self.ptr)
+            L.check(lib.dd_adam_step_scaled_clipped(ps.values.data_ptr(), ps.grads.data_ptr(), ps.m.data_ptr(), ps.v.data_ptr(), n, lr, beta1, beta2,
+                                                    eps, grad_scale, self.ptr, clipper.ptr, stream))
+        else:
+            L.check(lib.dd_adam_step_scaled(ps.values.data_ptr(), ps.grads.data_ptr(), ps.m.data_ptr(), ps.v.data_ptr(), n, lr, beta1, beta2, eps,
+                                            grad_scale, self.ptr, stream))
         L.check(lib.dd_scaler_update(self.ptr, c["growth"], c["backoff"], c["growth_interval"], c["min_scale"], c["max_scale"], stream))

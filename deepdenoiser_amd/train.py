@@ -36,7 +36,7 @@ import time
 import numpy as np
 import torch
 
-from . import loss_scale, summaries, tf_checkpoint, tfrecords
+from . import grad_clip, loss_scale, summaries, tf_checkpoint, tfrecords
 from .architecture import Architecture
 from .data_augmentation import DataAugmentation, DataAugmentationUsage
 from .metrics import MeanAccumulator
@@ -71,8 +71,26 @@ def parser():
     p.add_argument("--loss_scale", type=loss_scale.cli_value, default=None, metavar="{dynamic,<number>}",
                    help="Loss scale of the optimisation step: 'dynamic' keeps it on the device (halved on an inf / NaN gradient, whose step is skipped, "
                         "doubled after 2000 applied steps), a positive number fixes it.  Default: 4096 for f16, 1 for bf16 / f32.")
+    p.add_argument("--clip_norm", type=grad_clip.cli_value, default=None, metavar="X",
+                   help="Clip the gradients by their global norm (tf.clip_by_global_norm) on the device: they are multiplied by X / max(norm, X).  "
+                        "Overrides the optional \"gradient_clip_norm\" of Training.json; absent, null or 0: off.")
+    p.add_argument("--gradient_norms", action="store_true",
+                   help="Every --summary_steps steps also write gradient_norm/<variable> and weight_norm/<variable> of every variable and "
+                        "gradient_nonfinite_variables (the global gradient_norm and gradient_clip_coefficient are written whenever this or "
+                        "clipping is on).")
     p.add_argument("--seed", type=int, default=0, help="seed of the file / example shuffles and of the source index tuples (shared by all ranks)")
     return p
+
+
+def gradient_scalars(report, per_variable=False):
+    """[(tag, value)] of a grad_clip report: gradient_norm and gradient_clip_coefficient; per_variable (--gradient_norms): also
+    gradient_nonfinite_variables and gradient_norm/<variable>, weight_norm/<variable> of every variable, in creation order."""
+    out = [("gradient_norm", report["grad_norm"]), ("gradient_clip_coefficient", report["coef"])]
+    if per_variable:
+        out.append(("gradient_nonfinite_variables", report["nonfinite_variables"]))
+        out += [("gradient_norm/" + name, v["grad_norm"]) for name, v in report["variables"].items()]
+        out += [("weight_norm/" + name, v["weight_norm"]) for name, v in report["variables"].items()]
+    return out
 
 
 def evaluation_jsons(base, mode):
@@ -340,7 +358,8 @@ def main(args):
     directory = os.path.dirname(os.path.abspath(args.json_filename))
     aj = json.load(open(os.path.join(directory, tj["architecture"])))
     arch = Architecture(aj, source_data_format="channels_last", data_format=args.data_format, device="cuda:%d" % local, dtype=args.dtype,
-                        loss_scale=args.loss_scale)
+                        loss_scale=args.loss_scale, clip_norm=grad_clip.resolve_clip_norm(args.clip_norm, tj),
+                        track_gradient_norms=args.gradient_norms)
     base = tj["base_tfrecords_directory"] if os.path.isabs(tj["base_tfrecords_directory"]) else os.path.join(directory, tj["base_tfrecords_directory"])
     if "training" not in tj["modes"]:
         raise Exception("No training mode found.")
@@ -473,6 +492,10 @@ def main(args):
                 scaler = trainer.program.sync_adam_step()                # (the loss is about to be read back: the wait is paid for anyway)
                 if scaler is not None:
                     scalars = [("loss_scale", scaler["scale"]), ("skipped_steps", scaler["skipped_total"])] + scalars
+                # clipping / --gradient_norms: the tables of this step's reduction (every rank holds the same bytes; rank 0 writes)
+                norms = trainer.program.gradient_report() if writer is not None else None
+                if norms is not None:
+                    scalars = gradient_scalars(norms, per_variable=args.gradient_norms) + scalars
                 if writer is not None:
                     head = [("loss", float(mean_loss) / world), ("learning_rate", tj["learning_rate"]), ("batch_size", tj["batch_size"])]
                     if histos:      # ONE event: the scalars up to batch_size, the histograms, the tracked scalars (Training.py:676-698)

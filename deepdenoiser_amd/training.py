@@ -160,6 +160,8 @@ class Trainer:
         # Dynamic loss scale (loss_scale.py): the non-finite scan of adam() reads the WHOLE arena after the all-reduce.  A sum over the ranks
         # that has an inf / NaN term is itself inf / NaN, so every rank sees the overflow of any rank in the same data and takes the same
         # decision (skip and back off, or apply) without a collective of its own.
+        # Gradient clipping (grad_clip.py) likewise: its reduction reads the arena after reducer.wait(), in an order fixed by the chunk table and
+        # without atomics, so every rank computes the same norm and the same coefficient from the same bytes -- no collective of its own.
         prog.adam(grad_scale=self.reducer.grad_scale)
         return prog.loss_buf
 

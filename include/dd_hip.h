@@ -551,6 +551,50 @@ int dd_adam_step_scaled(float* params, const float* grads, float* m, float* v, l
  * cleared.  Conventional values: growth 2, backoff 0.5, growth_interval 2000, min_scale 1, max_scale 2^24. */
 int dd_scaler_update(dd_scaler_state* st, float growth, float backoff, int growth_interval, float min_scale, float max_scale, dd_stream stream);
 
+/* ---- gradient clipping by global norm with per-variable norms (csrc/dd_grad_norm.hip; replaces tf.clip_by_global_norm).  One segmented,
+ * fixed-order reduction over the flat gradient arena and, at the same indices, the value arena: two launches on the caller's stream, no
+ * floating-point atomics, so the same bytes give the same bytes on every run and on every rank.
+ * The host cuts every variable into chunks (deepdenoiser_amd/grad_clip.py, plan_chunks): at most DD_GRAD_CHUNK elements each, never across
+ * two variables, never over the padding words between variables (which are excluded from every sum and may hold anything), sorted by
+ * variable and, inside one, by offset; var_first[v] ... var_first[v + 1] are the chunks of variable v (n_vars + 1 entries). */
+#define DD_GRAD_CHUNK 4096
+#define DD_GRAD_PARTIAL_BYTES 24        /* scratch of the first launch per chunk */
+typedef struct {
+  long offset;            /* first element of the chunk in both arenas */
+  int length;             /* 1 ... DD_GRAD_CHUNK elements */
+  int variable;           /* index of the variable the chunk belongs to */
+} dd_grad_chunk;
+typedef struct {
+  double grad_sq;         /* sum of squares of the variable's finite STORED gradient elements (before grad_factor) */
+  double weight_sq;       /* sum of squares of the variable's values */
+  unsigned nonfinite;     /* gradient elements that are inf / NaN; they add to no sum */
+  unsigned reserved;      /* 0 */
+} dd_grad_var_norms;
+typedef struct {
+  float grad_norm;                /* |grad_factor| * sqrt(sum of grad_sq): the norm of the true gradient; +inf when any element is inf / NaN */
+  float coef;                     /* clip_norm / max(grad_norm, clip_norm); exactly 1 when clip_norm <= 0 or any element is inf / NaN */
+  float grad_factor;              /* what the Adam launch multiplies the stored gradients by: grad_scale, or grad_scale / st->scale */
+  unsigned nonfinite_variables;   /* variables with at least one inf / NaN gradient element */
+  unsigned nonfinite_total;       /* inf / NaN gradient elements of the arena */
+} dd_grad_clip;
+/* Stage 1 (one workgroup per chunk: sums of squares in double and the count of inf / NaN gradient elements, reduced in a fixed order into
+ * `partials`, n_chunks * DD_GRAD_PARTIAL_BYTES bytes) and stage 2 (one workgroup: every variable from its chunks in chunk order into
+ * var_norms[n_vars], the totals in variable order into *clip).  grad_factor is grad_scale when st is null and grad_scale / st->scale (read
+ * on the device, before the scaler's update) otherwise -- the factor of the Adam launch that follows.  clip_norm <= 0 only measures
+ * (coef = 1).  chunks, var_first, partials, var_norms and clip are device memory; the whole of var_norms and *clip is rewritten by every
+ * call.  grads and values 16-byte aligned.  The entry cannot see the device tables: that every chunk lies inside both arenas, that
+ * var_first has n_vars + 1 ascending entries ending in n_chunks and that the output buffers have the sizes above is the caller's
+ * responsibility (grad_clip.GradientClipper checks its plan against the arena length before it uploads it). */
+int dd_grad_norms(const float* grads, const float* values, const dd_grad_chunk* chunks, int n_chunks, const int* var_first, int n_vars,
+                  void* partials, dd_grad_var_norms* var_norms, dd_grad_clip* clip, float clip_norm, float grad_scale,
+                  const dd_scaler_state* st, dd_stream stream);
+/* The two Adam launches with the gradient grads * grad_factor * clip->coef (clip->coef read on the device).  With clip->coef == 1 the
+ * results are bit-identical to those of the unclipped entries; the skip on st->found_nonfinite is unchanged. */
+int dd_adam_step_clipped(float* params, const float* grads, float* m, float* v, long n, float lr_t, float beta1, float beta2,
+                         float eps, float grad_scale, const dd_grad_clip* clip, dd_stream stream);
+int dd_adam_step_scaled_clipped(float* params, const float* grads, float* m, float* v, long n, double lr, double beta1, double beta2,
+                                float eps, float grad_scale, const dd_scaler_state* st, const dd_grad_clip* clip, dd_stream stream);
+
 /* ---- inference stitch (Prediction.py:384-441): copy crop windows of row-major tiles into the frame */
 typedef struct { int tile; int crop_y0, crop_y1, crop_x0, crop_x1; int dst_img, dst_y, dst_x; } dd_stitch_entry;
 /* frames: [n_img, frame_h, frame_w, ldf]; entry copies tiles[tile][crop] to frames[dst_img] at (dst_y, dst_x) */
