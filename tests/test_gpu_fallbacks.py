@@ -47,6 +47,10 @@ CASES = {   # name: (environment of the child, -k expression[, test file (defaul
     # the per-pixel kernel in its own process)
     "loss_ops_on_the_older_kernel": ({"DD_LOSS_SIMPLE": "0", "DD_LOSS_GENERAL": "0"},
                                      "not wrap_flat and not wrap_pixel and not bit_identical", "test_gpu_loss_ops.py"),
+    # the op-level 65 - 96-channel rows (tests/test_gpu_conv_bwd_ops.py) with the switch dd_conv3x3_bwd caches in a static turned off: each layer
+    # runs as one launch per 64 output channels of csrc/dd_conv_bwd.hip, the second accumulating into dx -- the same float64 reference, gated
+    # with one rounding per launch
+    "conv_bwd_ops_65_to_96_as_per_64_launches": ({"DD_CONV_BWD96": "0"}, "test_conv3x3_bwd_65_to_96", "test_gpu_conv_bwd_ops.py"),
 }
 
 
