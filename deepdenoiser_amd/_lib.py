@@ -44,7 +44,7 @@ SYMBOLS = (
     "dd_stitch", "dd_recombine", "dd_probe_tr16", "dd_masked_add", "dd_zero_stuff", "dd_zero_unstuff", "dd_convert_channels",
     "dd_augment", "dd_loss_mask_sums", "dd_crc32c", "dd_extract_tiles", "dd_compose_net_fwd", "dd_compose_net_bwd",
     "dd_kpcn_head_fwd", "dd_kpcn_head_bwd", "dd_kpcn_head_bwd_multi", "dd_assemble_input", "dd_assemble_input_frames", "dd_conv3x3_bwd", "dd_conv3x3_bwd_multi", "dd_convt2x2_fwd", "dd_convt2x2_bwd", "dd_conv3x3_ks",
-    "dd_conv_pw_count", "dd_wgrad_pw_count", "dd_space_to_depth2", "dd_convt3_wgrad", "dd_compose_stream_plan", "dd_compose_bwd_scratch_bytes",
+    "dd_conv_pw_count", "dd_wgrad_pw_count", "dd_conv_route_count", "dd_space_to_depth2", "dd_convt3_wgrad", "dd_compose_stream_plan", "dd_compose_bwd_scratch_bytes",
     "dd_loss_msssim_scratch_bytes", "dd_loss_msssim_fwd", "dd_loss_msssim_bwd", "dd_loss_msssim_values",
     "dd_loss_metrics_scratch_bytes", "dd_loss_metrics", "dd_loss_head_path_count",
     "dd_loss_head_dscale", "dd_loss_msssim_bwd_dscale", "dd_grads_nonfinite", "dd_adam_step_scaled", "dd_scaler_update",
@@ -52,6 +52,17 @@ SYMBOLS = (
     "dd_nonfinite_scan", "dd_nonfinite_repair", "dd_frame_quality_scratch_bytes", "dd_frame_quality", "dd_stitch_blend",
     "dd_grad_norms", "dd_adam_step_clipped", "dd_adam_step_scaled_clipped",
 )
+
+
+# enum dd_conv_route (include/dd_hip.h): the kernels dd_conv_igemm / dd_conv3x3_ks / dd_conv_wgrad route a call to, in the header's order
+ROUTES = ("igemm_resident", "igemm_streamed", "igemm_ws", "rw_6_2", "rw12", "rw12_mask", "rw12_res", "rw8_kc2", "rw8_kc4", "rw8_kc4_mask", "pw",
+          "ks", "ks_pw_taps", "wgrad_dma", "wgrad_reg", "wgrad_pw", "wgrad_stacked")
+
+
+def route_counts():
+    """{route name: launches this process sent down it} (dd_conv_route_count)."""
+    lib = load()
+    return {name: lib.dd_conv_route_count(r) for r, name in enumerate(ROUTES)}
 
 
 class ConvT3WgradArgs(C.Structure):
@@ -312,6 +323,8 @@ def load():
     lib.dd_conv_pw_count.restype = C.c_long
     lib.dd_wgrad_pw_count.argtypes = []
     lib.dd_wgrad_pw_count.restype = C.c_long
+    lib.dd_conv_route_count.argtypes = [i]
+    lib.dd_conv_route_count.restype = C.c_long
     lib.dd_colsum.argtypes = [vp, i, i, l, vp, i, vp]
     lib.dd_colsum_segments.argtypes = [vp, i, i, l, i, vp, i, vp, i, vp]
     lib.dd_maxpool_fwd.argtypes = [vp, i, vp, i, vp, i, i, i, i, i, i, i, i, vp]

@@ -34,6 +34,12 @@ void dd_set_error(const char* fmt, ...);
     }                                                                       \
   } while (0)
 
+// ------------------------------------------------------------------------------------------------ which kernel ran (host side only)
+// (csrc/dd_conv_igemm.hip) One plain host counter per enum dd_conv_route, read by dd_conv_route_count(); DD_ROUTE_TAKEN stands next to the
+// hipLaunchKernelGGL it counts.
+extern long dd_route_counts[DD_ROUTE_COUNT];
+#define DD_ROUTE_TAKEN(route) (++dd_route_counts[route])
+
 // ------------------------------------------------------------------------------------------------ per-device launch state
 // (csrc/dd_pointwise.hip) One process may drive several devices: what the launchers cache is keyed by the CURRENT device.
 int dd_device_cus();                          // compute units of the current device

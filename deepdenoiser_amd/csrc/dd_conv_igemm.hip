@@ -815,6 +815,7 @@ int launch(const ConvP& p, int nslabs, hipStream_t stream) {
   dd_allow_max_lds(reinterpret_cast<const void*>(conv_igemm_kernel<T, NT, HALO, RESIDENT>));
   const int per_cu = (int)((160 * 1024) / lds) >= 2 ? 2 : 1;   // two resident workgroups overlap each other's memory phases
   long wgs = grid_size((long)dd_device_cus() * per_cu, p);
+  DD_ROUTE_TAKEN(RESIDENT ? DD_ROUTE_IGEMM_RESIDENT : DD_ROUTE_IGEMM_STREAMED);
   hipLaunchKernelGGL((conv_igemm_kernel<T, NT, HALO, RESIDENT>), dim3((unsigned)wgs), dim3(256), lds, stream, p);
   DD_LAUNCH_CHECK();
   return DD_OK;
@@ -832,6 +833,7 @@ int launch_ws(const ConvP& p, int nslabs, hipStream_t stream) {
   const size_t lds = (size_t)PatchDim<HALO>::NPIX * DD_LDS_ROW + (size_t)DD_TILE * DD_TILE * DD_LDS_ROW + ws_weight_bytes(p, NT) + NT * 16 * sizeof(float);
   dd_allow_max_lds(reinterpret_cast<const void*>(conv_igemm_ws_kernel<T, NT, HALO>));
   long wgs = grid_size((long)dd_device_cus(), p);
+  DD_ROUTE_TAKEN(DD_ROUTE_IGEMM_WS);
   hipLaunchKernelGGL((conv_igemm_ws_kernel<T, NT, HALO>), dim3((unsigned)wgs), dim3(512), lds, stream, p);
   DD_LAUNCH_CHECK();
   return DD_OK;
@@ -906,6 +908,10 @@ int dispatch(ConvP& p, hipStream_t stream) {
 
 }  // namespace
 
+// which kernel ran: one host counter per route (include/dd_hip.h, enum dd_conv_route), incremented by DD_ROUTE_TAKEN next to each launch
+long dd_route_counts[DD_ROUTE_COUNT] = {0};
+extern "C" long dd_conv_route_count(int route) { return route >= 0 && route < DD_ROUTE_COUNT ? dd_route_counts[route] : -1; }
+
 bool dd_conv_rw_eligible(const dd_conv_args* a);
 int dd_conv_rw_launch(const dd_conv_args* a, hipStream_t stream);
 bool dd_conv_pw_eligible(const dd_conv_args* a);
@@ -923,7 +929,8 @@ extern "C" int dd_conv_igemm(const dd_conv_args* a, dd_stream stream) {
   DD_REQUIRE(a->cin > 0 && a->cin % per16 == 0 && a->ldx % per16 == 0, "dd_conv_igemm: cin=%d ldx=%d must be multiples of %d", a->cin, a->ldx, per16);
   DD_REQUIRE(a->k_pad >= a->cin && (a->k_pad * esz) % 64 == 0, "dd_conv_igemm: k_pad=%d invalid for cin=%d", a->k_pad, a->cin);
   DD_REQUIRE(a->n_pad % 16 == 0 && a->n > 0 && a->n <= a->n_pad && a->n % 4 == 0, "dd_conv_igemm: n=%d n_pad=%d invalid", a->n, a->n_pad);
-  DD_REQUIRE(!pixshuf || (a->n % 16 == 0), "dd_conv_igemm: DD_PIXSHUF needs 4*cout %% 16 == 0");
+  // (every epilogue stores whole 16-byte vectors of ONE output pixel: with a narrower cout a vector would straddle two parities (a, b))
+  DD_REQUIRE(!pixshuf || (a->n % (4 * per16) == 0), "dd_conv_igemm: DD_PIXSHUF needs cout = n / 4 = %d %% %d == 0 (16-byte vectors per output pixel)", a->n / 4, per16);
   DD_REQUIRE(a->ldy % 4 == 0 && (!a->res || a->ldres % 4 == 0) && (!a->mask || a->ldmask % 4 == 0), "dd_conv_igemm: ld must be multiple of 4");
   DD_REQUIRE(a->B > 0 && a->H > 0 && a->W > 0, "dd_conv_igemm: empty grid");
   DD_REQUIRE(((uintptr_t)a->x % 16) == 0 && ((uintptr_t)a->wp % 16) == 0 && ((uintptr_t)a->y % 16) == 0, "dd_conv_igemm: pointers must be 16-byte aligned");

@@ -436,6 +436,7 @@ extern "C" int dd_conv3x3_ks(const dd_conv_ks_args* a, dd_stream stream) {
     }
   for (int i = ns; i < KS_MAX_SUB; ++i) m.sub[i] = KsSub{0, 1, 0, 0, 0, 0};
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  DD_ROUTE_TAKEN(DD_ROUTE_KS);
   const size_t smem = 2 * (size_t)KS_BUF + (KS_WLDS ? 2 * (size_t)KS_WBUF_MAX : 0);      // two input buffers + two weight buffers (narrow workgroups)
   if (a->dtype == DD_BF16) {
     dd_allow_max_lds(reinterpret_cast<const void*>(conv_ks_kernel<bf16_t>));

@@ -604,6 +604,7 @@ static int pw_plan_and_launch(PwP& p, int dtype, bool in_relu, hipStream_t s) {
 
 int dd_conv_pw_launch(const dd_conv_args* a, hipStream_t s) {
   ++g_pw_launches;
+  DD_ROUTE_TAKEN(DD_ROUTE_PW);
   PwP p;
   p.x = a->x; p.wp = a->wp; p.bias = a->bias; p.mask = a->mask; p.y = a->y;
   p.ldx = a->ldx; p.ldy = a->ldy; p.ldmask = a->ldmask; p.cinv = a->cin; p.n = a->n; p.n_pad = a->n_pad; p.k_pad = a->k_pad;
@@ -627,6 +628,7 @@ bool dd_conv_pw_taps_eligible(const dd_conv_ks_args* a) {
 
 int dd_conv_pw_taps_launch(const dd_conv_ks_args* a, hipStream_t s) {
   ++g_pw_launches;
+  DD_ROUTE_TAKEN(DD_ROUTE_KS_PW_TAPS);
   PwP p;
   p.x = a->x; p.wp = a->wp; p.bias = a->bias; p.mask = a->mask; p.y = a->y;
   p.ldx = a->ldx; p.ldy = a->ldy; p.ldmask = a->ldmask; p.cinv = a->cin; p.n = a->n; p.n_pad = a->n_pad; p.k_pad = a->k_pad;
@@ -695,6 +697,7 @@ static int pwg_plan_and_launch(PwgP& p, int dtype, hipStream_t s) {
 
 int dd_wgrad_pw_launch(const dd_wgrad_args* a, hipStream_t s) {
   ++g_pwg_launches;
+  DD_ROUTE_TAKEN(DD_ROUTE_WGRAD_PW);
   PwgP p;
   p.p = a->p; p.q = a->q; p.out = a->out; p.bias_out = a->bias_out; p.bias_mode = a->bias_mode;
   p.ldp = a->ldp; p.ldq = a->ldq; p.m = a->m; p.n = a->n; p.mv = (a->m + 7) / 8 * 8; p.nv = (a->n + 7) / 8 * 8;

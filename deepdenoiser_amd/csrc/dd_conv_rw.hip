@@ -550,18 +550,25 @@ int dd_conv_rw_launch(const dd_conv_args* a, hipStream_t stream) {
   if (ksplit > total) ksplit = total;
   p.ksplit = (int)ksplit;
   if (masked12) {
+    DD_ROUTE_TAKEN(DD_ROUTE_RW12_MASK);
     if (a->dtype == DD_BF16) rw8_launch<bf16_t, 3, 12, 1>(p, stream); else rw8_launch<f16_t, 3, 12, 1>(p, stream);
   } else if (res12) {
+    DD_ROUTE_TAKEN(DD_ROUTE_RW12_RES);
     if (a->dtype == DD_BF16) rw8_launch<bf16_t, 3, 12, 2>(p, stream); else rw8_launch<f16_t, 3, 12, 2>(p, stream);
   } else if (twelve) {
+    DD_ROUTE_TAKEN(DD_ROUTE_RW12);
     if (a->dtype == DD_BF16) rw8_launch<bf16_t, 3, 12>(p, stream); else rw8_launch<f16_t, 3, 12>(p, stream);
   } else if (six) {
+    DD_ROUTE_TAKEN(DD_ROUTE_RW_6_2);
     if (a->dtype == DD_BF16) rw_launch_flags<bf16_t, 3>(p, stream); else rw_launch_flags<f16_t, 3>(p, stream);
   } else if (a->cin <= 64) {
+    DD_ROUTE_TAKEN(DD_ROUTE_RW8_KC2);
     if (a->dtype == DD_BF16) rw8_launch<bf16_t, 2>(p, stream); else rw8_launch<f16_t, 2>(p, stream);
   } else if (a->mask) {
+    DD_ROUTE_TAKEN(DD_ROUTE_RW8_KC4_MASK);
     if (a->dtype == DD_BF16) rw8_launch<bf16_t, 4, 8, 1>(p, stream); else rw8_launch<f16_t, 4, 8, 1>(p, stream);
   } else {
+    DD_ROUTE_TAKEN(DD_ROUTE_RW8_KC4);
     if (a->dtype == DD_BF16) rw8_launch<bf16_t, 4>(p, stream); else rw8_launch<f16_t, 4>(p, stream);
   }
   DD_LAUNCH_CHECK();

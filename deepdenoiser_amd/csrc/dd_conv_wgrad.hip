@@ -711,6 +711,7 @@ static int launch_dma(WgradP& p, hipStream_t stream) {
   const long blocks = p.cstart[p.ncombo];
   const bool relu = (p.flags & DD_IN_RELU) != 0;
   const int mode = p.taps == 1 ? 2 : (p.m <= 32 && p.n <= 32) ? 1 : 0;
+  DD_ROUTE_TAKEN(p.stack_blocks ? DD_ROUTE_WGRAD_STACKED : DD_ROUTE_WGRAD_DMA);
   if (mode == 2) { if (relu) launch_dma_mode<T, true, 2>(p, blocks, stream); else launch_dma_mode<T, false, 2>(p, blocks, stream); }
   else if (mode == 1) { if (relu) launch_dma_mode<T, true, 1>(p, blocks, stream); else launch_dma_mode<T, false, 1>(p, blocks, stream); }
   else { if (relu) launch_dma_mode<T, true, 0>(p, blocks, stream); else launch_dma_mode<T, false, 0>(p, blocks, stream); }
@@ -725,6 +726,7 @@ int launch(const WgradP& p, hipStream_t stream) {
   dd_allow_max_lds(reinterpret_cast<const void*>(wgrad_kernel<T, TAPS>), 96 * 1024);
   const long blocks = (long)p.ksplit * p.mslices * p.nslices;
   dd_det_sync();
+  DD_ROUTE_TAKEN(DD_ROUTE_WGRAD_REG);
   hipLaunchKernelGGL((wgrad_kernel<T, TAPS>), dim3((unsigned)blocks), dim3(256), lds, stream, p);
   DD_LAUNCH_CHECK();
   return DD_OK;

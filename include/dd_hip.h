@@ -72,7 +72,7 @@ typedef struct {
   const float* bias; int nbias;        /* fp32 bias and its length (nbias <= n), or NULL */
   const void* res; int ldres;          /* residual added before activation, or NULL */
   const void* mask; int ldmask;        /* y *= (mask > 0), or NULL (ReLU backward fused into the producer) */
-  void* y; int ldy; int n;             /* output channels actually stored (n <= n_pad, n % 4 == 0) */
+  void* y; int ldy; int n;             /* output channels actually stored (n <= n_pad, n % 4 == 0; DD_PIXSHUF: cout = n / 4 a multiple of 16 bytes) */
   int B, H, W;                         /* GEMM-row pixel grid: output grid, except DD_PIXSHUF where it is the input grid */
   int taps; int flags; int dtype;
 } dd_conv_args;
@@ -82,6 +82,31 @@ int dd_conv_igemm(const dd_conv_args* a, dd_stream stream);
  * to assert that the kernel they mean to check is the one that ran. */
 long dd_conv_pw_count(void);
 long dd_wgrad_pw_count(void);   /* ... and dd_conv_wgrad calls routed to its weight-gradient counterpart (taps == 1, m or n above 64 channels) */
+/* The same for EVERY kernel dd_conv_igemm, dd_conv3x3_ks and dd_conv_wgrad may route a call to: a host-side count per route, incremented next
+ * to the launch it counts (no kernel, launch geometry or dispatch rule depends on it).  dd_conv_route_count(route) is the number of launches
+ * this process sent down that route; -1 for a route it does not know.  Tests name the route a case must take and assert that exactly that
+ * counter moved. */
+enum dd_conv_route {
+  DD_ROUTE_IGEMM_RESIDENT = 0,  /* conv_igemm_kernel, weights resident in LDS (csrc/dd_conv_igemm.hip) */
+  DD_ROUTE_IGEMM_STREAMED,      /* conv_igemm_kernel, weights streamed slab by slab */
+  DD_ROUTE_IGEMM_WS,            /* conv_igemm_ws_kernel (wave-specialised, 2-byte storage) */
+  DD_ROUTE_RW_6_2,              /* conv_rw_kernel: 65..96 input channels, 6 compute + 2 I/O waves, any epilogue (csrc/dd_conv_rw.hip) */
+  DD_ROUTE_RW12,                /* conv_rw8_kernel<KC = 3, 12 waves>: 65..96 input channels, bias / ReLU */
+  DD_ROUTE_RW12_MASK,           /* ... with the ReLU-backward mask tile */
+  DD_ROUTE_RW12_RES,            /* ... with a residual operand */
+  DD_ROUTE_RW8_KC2,             /* conv_rw8_kernel<KC = 2>: 17..64 input channels */
+  DD_ROUTE_RW8_KC4,             /* conv_rw8_kernel<KC = 4>: 97..128 input channels */
+  DD_ROUTE_RW8_KC4_MASK,        /* ... with the ReLU-backward mask tile */
+  DD_ROUTE_PW,                  /* conv_pw_kernel from dd_conv_igemm (csrc/dd_conv_pw.hip) */
+  DD_ROUTE_KS,                  /* conv_ks_kernel (csrc/dd_conv_ks.hip) */
+  DD_ROUTE_KS_PW_TAPS,          /* dd_conv3x3_ks routed to conv_pw_kernel's tap form (dd_conv_pw_taps_launch) */
+  DD_ROUTE_WGRAD_DMA,           /* wgrad_dma_kernel, plain form (csrc/dd_conv_wgrad.hip) */
+  DD_ROUTE_WGRAD_REG,           /* wgrad_kernel (register-staged) */
+  DD_ROUTE_WGRAD_PW,            /* wgrad_pw_kernel from dd_conv_wgrad (csrc/dd_conv_pw.hip) */
+  DD_ROUTE_WGRAD_STACKED,       /* wgrad_dma_kernel, stacked dense-block form */
+  DD_ROUTE_COUNT
+};
+long dd_conv_route_count(int route);
 
 /* ---- weight gradient on MFMA: out[t][m][n] += sum_{b,p} in(P)[b,map_t(p),m] * Q[b,p,n]   (fp32 atomics)
  * conv2d:            P = layer input x, Q = pre-activation output gradient -> out = dKernel HWIO

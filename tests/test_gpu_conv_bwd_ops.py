@@ -17,14 +17,15 @@ import pytest
 import torch
 
 import conv_bwd_ref as R
+import conv_ops_util as U
 from deepdenoiser_amd import _lib as L
-from gpu_util import ACC32, ROUND, check, gate
+from gpu_util import ACC32, ROUND, check
 
 pytestmark = pytest.mark.gpu
-SENTINEL = 12288.0      # exact in fp32, bf16 and fp16
 PAD_OLD = 0.5           # what the pad channels cin..cinv-1 of an accumulated-into dx hold before the launch
-G = 4                   # guard words before and after dw / db (16 bytes: the arrays stay 16-byte aligned)
-DT = {"bf16": (L.DD_BF16, torch.bfloat16), "f16": (L.DD_F16, torch.float16)}
+DT = {k: U.DT[k] for k in ("bf16", "f16")}
+SENTINEL, G, View, Guarded = U.SENTINEL, U.G, U.View, U.Guarded      # shared with tests/test_gpu_conv_fwd_ops.py (tests/conv_ops_util.py)
+_stream, _bits, _pack, _gated = U.stream, U.bits, U.pack, U.gated
 # libdd_hip.so reads the switch once per process: `e && e[0] == '0'` turns the 65..96 kernel off and those layers run one launch per 64 channels
 BWD96_OFF = os.environ.get("DD_CONV_BWD96", "1")[:1] == "0"
 
@@ -32,10 +33,6 @@ BWD96_OFF = os.environ.get("DD_CONV_BWD96", "1")[:1] == "0"
 def _need_gpu():
     if not torch.cuda.is_available():
         pytest.skip("no GPU")
-
-
-def _stream():
-    return torch.cuda.current_stream().cuda_stream
 
 
 def _cus():
@@ -48,84 +45,6 @@ def _ids(cases):
 
 def _r8(c):
     return R.round_up(c, 8)
-
-
-class View:
-    """[B, H, W, C] values as channels [off, off + C) of a buffer of row length ld: channels up to `cv` zero, every other channel the sentinel."""
-
-    def __init__(self, shape, C_, cv, ld, off, dtype, values=None, pad=0.0):
-        self.C, self.cv, self.ld, self.off = C_, cv, ld, off
-        self.buf = torch.full(tuple(shape) + (ld,), SENTINEL, dtype=DT[dtype][1], device="cuda")
-        self.buf[..., off + C_:off + cv] = pad
-        if values is not None:
-            self.buf[..., off:off + C_] = values.to(DT[dtype][1]).cuda()
-        self.before = self.buf.clone()
-
-    @property
-    def ptr(self):
-        return self.buf.data_ptr() + self.off * self.buf.element_size()
-
-    def values(self):
-        return self.buf[..., self.off:self.off + self.C].double().cpu()
-
-    def pads(self):
-        return self.buf[..., self.off + self.C:self.off + self.cv].double().cpu()
-
-    def neighbours_intact(self):
-        return bool((self.buf[..., :self.off] == SENTINEL).all()) and bool((self.buf[..., self.off + self.cv:] == SENTINEL).all())
-
-    def unchanged(self):
-        return torch.equal(self.buf.view(torch.int16), self.before.view(torch.int16))
-
-
-class Guarded:
-    """n fp32 words (zero, or `values`) between G sentinel words on either side."""
-
-    def __init__(self, n, values=None):
-        self.n = n
-        self.buf = torch.full((n + 2 * G,), SENTINEL, dtype=torch.float32, device="cuda")
-        self.buf[G:G + n] = 0.0 if values is None else values.float().reshape(-1).cuda()
-
-    @property
-    def ptr(self):
-        return self.buf.data_ptr() + 4 * G
-
-    def values(self):
-        return self.buf[G:G + self.n].double().cpu()
-
-    def guards_intact(self):
-        return bool((self.buf[:G] == SENTINEL).all()) and bool((self.buf[G + self.n:] == SENTINEL).all())
-
-
-def _bits(t):
-    return t.contiguous().view(torch.int16)
-
-
-def _pack(lib, kind, role, master, cin, cout, dtype):
-    """dd_pack_weights with the strides and n_pad / k_pad rule of engine.Layer.packed(role); the image is compared bit for bit with the numpy
-    restatement (padding exactly zero) and must end where it should.  Returns (device image, n_pad, k_pad)."""
-    taps, n, k, st, sn, sk, flip = R.pack_params(kind, role, cin, cout)
-    n_pad, k_pad = R.pack_dims(n, k)
-    src = master.float().contiguous().cuda()
-    total = taps * n_pad * k_pad
-    dst = torch.full((total + 8,), SENTINEL, dtype=DT[dtype][1], device="cuda")
-    L.check(lib.dd_pack_weights(src.data_ptr(), dst.data_ptr(), DT[dtype][0], taps, n, k, n_pad, k_pad, st, sn, sk, flip, _stream()))
-    torch.cuda.synchronize()
-    want = R.pack_weights(src.cpu().numpy(), dtype, taps, n, k, n_pad, k_pad, st, sn, sk, flip)
-    assert want.numel() == total
-    assert torch.equal(_bits(dst[:total].cpu()), _bits(want)), "dd_pack_weights %s %s %dx%d %s: image differs from the restatement" % (kind, role, cin, cout, dtype)
-    assert bool((dst[total:] == SENTINEL).all()), "dd_pack_weights wrote past its image"
-    return dst, n_pad, k_pad
-
-
-def _gated(name, got, ref, gate_t):
-    got = got.double().cpu()
-    assert tuple(got.shape) == tuple(ref.shape), (name, tuple(got.shape), tuple(ref.shape))
-    assert bool(torch.isfinite(got).all()), name + ": non-finite values"
-    w = R.worst_ratio(got, ref, gate_t)
-    print("%-84s worst error / gate %.3f over %d elements" % (name, w, ref.numel()))
-    gate(name, w, 1.0)
-    return w
 
 
 def _check_fp32(name, arr, ref, budget, dtype):

@@ -51,6 +51,14 @@ CASES = {   # name: (environment of the child, -k expression[, test file (defaul
     # runs as one launch per 64 output channels of csrc/dd_conv_bwd.hip, the second accumulating into dx -- the same float64 reference, gated
     # with one rounding per launch
     "conv_bwd_ops_65_to_96_as_per_64_launches": ({"DD_CONV_BWD96": "0"}, "test_conv3x3_bwd_65_to_96", "test_gpu_conv_bwd_ops.py"),
+    # the op-level forward / weight-gradient cases (tests/test_gpu_conv_fwd_ops.py), which compute the route each call must take from these very
+    # switches and assert its counter: first with the round-1 library (the 2-byte cases on the plain conv_igemm_kernel and the register-staged
+    # wgrad_kernel, the stacked weight gradient refused with its documented error), then with the newer register-weight kernels off (65 - 96
+    # input channels on the 6 + 2 wave kernel, the rest of the family on the implicit-GEMM kernels)
+    "conv_fwd_ops_on_the_round1_kernels": ({"DD_CONV_WS": "0", "DD_CONV_RW": "0", "DD_WGRAD_DMA": "0", "DD_CONV_PW": "0"}, "test_conv",
+                                           "test_gpu_conv_fwd_ops.py"),
+    "conv_fwd_ops_on_the_older_register_weight_kernels": ({"DD_CONV_RW12": "0", "DD_CONV_RW12_MASK": "0", "DD_CONV_RW8_MASK": "0", "DD_CONV_RW8": "0"},
+                                                          "test_conv", "test_gpu_conv_fwd_ops.py"),
 }
 
 
