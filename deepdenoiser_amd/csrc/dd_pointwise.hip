@@ -86,6 +86,9 @@ extern "C" int dd_crc32c(const void* data, size_t n, uint32_t crc, uint32_t* out
 
 #define S(stream) reinterpret_cast<hipStream_t>(stream)
 static inline unsigned grid_for(long n, int block = 256) { return (unsigned)((n + block - 1) / block); }
+// the vector loads and stores of the single-pass kernels below: every operand starts on a whole vector (NULL, an optional operand, passes)
+static inline bool vec_aligned(const void* p, size_t bytes) { return ((uintptr_t)p % bytes) == 0; }
+static inline size_t elem_size(int dtype) { return dtype == DD_F32 ? 4 : 2; }
 
 // ------------------------------------------------------------------------------------------------ pack weights
 template <typename T>
@@ -167,6 +170,7 @@ extern "C" int dd_colsum(const void* x, int ld, int c, long rows, float* out, in
       return dd_colsum_segments(x, ld, c, rows, 1, out, c, &row0, dtype, stream);
     }
   }
+  DD_REQUIRE(dd_dtype_ok(dtype), "dd_colsum: bad dtype %d", dtype);
   dim3 g((unsigned)min((rows + 3) / 4, 1024L), (unsigned)((c + 63) / 64));
   dd_det_sync();
   DD_DISPATCH_DTYPE(dtype, T, hipLaunchKernelGGL(colsum_kernel<T>, g, dim3(256), 0, S(stream), (const T*)x, ld, c, rows, out));
@@ -316,6 +320,7 @@ extern "C" int dd_maxpool_fwd(const void* x, int ldx, void* y, int ldy, uint8_t*
   const int per16 = dtype == DD_F32 ? 4 : 8;
   DD_REQUIRE(dd_dtype_ok(dtype), "bad dtype %d", dtype);
   DD_REQUIRE(x && y && C % per16 == 0 && ldx % per16 == 0 && ldy % per16 == 0, "dd_maxpool_fwd: C, ld must be multiples of %d", per16);      // (idx may be NULL: forward only)
+  DD_REQUIRE(vec_aligned(x, 16) && vec_aligned(y, 16) && vec_aligned(idx, per16), "dd_maxpool_fwd: x, y must be 16-byte aligned, idx %d-byte aligned", per16);
   DD_REQUIRE(pool * pool < 255, "dd_maxpool_fwd: pool=%d too large", pool);
   int OH, OW, pby, pbx;
   same_pad(H, pool, stride, &OH, &pby); same_pad(W, pool, stride, &OW, &pbx);
@@ -460,7 +465,9 @@ extern "C" int dd_maxpool_bwd(const void* dy, int lddy, const uint8_t* idx, void
                               int C, int B, int H, int W, int pool, int stride, int accumulate, int dtype, dd_stream stream) {
   const int per16 = dtype == DD_F32 ? 4 : 8;
   DD_REQUIRE(dd_dtype_ok(dtype), "bad dtype %d", dtype);
-  DD_REQUIRE(dy && idx && dx && C % per16 == 0 && lddy % per16 == 0 && lddx % per16 == 0, "dd_maxpool_bwd: C, ld must be multiples of %d", per16);
+  DD_REQUIRE(dy && idx && dx && C % per16 == 0 && lddy % per16 == 0 && lddx % per16 == 0 && (!mask || ldmask % per16 == 0), "dd_maxpool_bwd: C, ld must be multiples of %d", per16);
+  DD_REQUIRE(vec_aligned(dy, 16) && vec_aligned(dx, 16) && vec_aligned(mask, 16) && vec_aligned(idx, per16),
+             "dd_maxpool_bwd: dy, dx, mask must be 16-byte aligned, idx %d-byte aligned", per16);
   int OH, OW, pby, pbx;
   same_pad(H, pool, stride, &OH, &pby); same_pad(W, pool, stride, &OW, &pbx);
   if (pool_s2_ok(pool, stride, B, H, W, lddx > C ? lddx : C)) {
@@ -1125,6 +1132,7 @@ __global__ void compose_pack_kernel(const float* __restrict__ small, int lds, co
 extern "C" int dd_compose_pack(const float* small, int lds, const float* fine, int ldf, void* dst, int ld, int c_pad,
                                int B, int H, int W, int dtype, dd_stream stream) {
   DD_REQUIRE(small && fine && dst && H % 2 == 0 && W % 2 == 0 && c_pad >= 6 && c_pad <= ld, "dd_compose_pack: bad arguments");
+  DD_REQUIRE(dd_dtype_ok(dtype), "dd_compose_pack: bad dtype %d", dtype);
   const long total = (long)B * H * W;
   DD_DISPATCH_DTYPE(dtype, T, hipLaunchKernelGGL(compose_pack_kernel<T>, dim3(grid_for(total)), dim3(256), 0, S(stream), small, lds, fine, ldf, (T*)dst, ld, c_pad, B, H, W));
   DD_LAUNCH_CHECK();
@@ -1166,6 +1174,7 @@ __global__ void compose_blend_fwd_kernel(const float* __restrict__ small, int ld
 extern "C" int dd_compose_blend_fwd(const float* small, int lds, const float* fine, int ldf, const void* wl, int ldw,
                                     float* out, int ldo, int B, int H, int W, int dtype, dd_stream stream) {
   DD_REQUIRE(small && fine && wl && out && H % 2 == 0 && W % 2 == 0, "dd_compose_blend_fwd: bad arguments");
+  DD_REQUIRE(dd_dtype_ok(dtype), "dd_compose_blend_fwd: bad dtype %d", dtype);
   const long total = (long)B * (H / 2) * (W / 2);
   DD_DISPATCH_DTYPE(dtype, T, hipLaunchKernelGGL(compose_blend_fwd_kernel<T>, dim3(grid_for(total)), dim3(256), 0, S(stream), small, lds, fine, ldf, (const T*)wl, ldw, out, ldo, B, H, W));
   DD_LAUNCH_CHECK();
@@ -1187,12 +1196,16 @@ __global__ void compose_blend_bwd_kernel(const float* __restrict__ dout, int ldd
   const int b = (int)(r / h2);
   const float* s = small + i * lds;
   long pix[4];
-  float f[4][3], g[4][3], w[4], wlv[4], low[3] = {0.f, 0.f, 0.f}, tsum[3] = {0.f, 0.f, 0.f};
+  float f[4][3], g[4][3], w[4], omw[4], wlv[4], low[3] = {0.f, 0.f, 0.f}, tsum[3] = {0.f, 0.f, 0.f};
 #pragma unroll
   for (int k = 0; k < 4; ++k) {
     pix[k] = ((long)b * H + 2 * qy + (k >> 1)) * W + 2 * qx + (k & 1);
     wlv[k] = ld1<T>(wl + pix[k] * ldw);
-    w[k] = sigmoidf(wlv[k]);
+    // w = sigmoid(wl) as sigmoidf() computes it, and 1 - w = e / (1 + e) = e * w without the subtraction: for a large wl, 1.f - w cancels (at wl = 8
+    // it keeps 12 of 24 bits, and dwl of such a pixel was off by up to 2e-4 relative: tests/test_gpu_pointwise_ops.py)
+    const float e = __expf(-wlv[k]);
+    w[k] = 1.f / (1.f + e);
+    omw[k] = e * w[k];
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
       f[k][c] = fine[pix[k] * ldf + c];
@@ -1211,7 +1224,7 @@ __global__ void compose_blend_bwd_kernel(const float* __restrict__ dout, int ldd
       dw += g[k][c] * (s[c] - low[c]);
       dfine[pix[k] * lddf + c] = g[k][c] - 0.25f * tsum[c];
     }
-    const float d = wlv[k] > 0.f ? dw * w[k] * (1.f - w[k]) : 0.f;
+    const float d = wlv[k] > 0.f ? dw * w[k] * omw[k] : 0.f;
     T* o = dwl + pix[k] * lddw;
     o[0] = Elem<T>::from_f32(d);
     for (int c = 1; c < dw_pad; ++c) o[c] = Elem<T>::from_f32(0.f);
@@ -1221,6 +1234,7 @@ extern "C" int dd_compose_blend_bwd(const float* dout, int lddo, const float* sm
                                     const void* wl, int ldw, float* dsmall, int ldds, int accumulate_small, float* dfine, int lddf,
                                     void* dwl, int lddw, int dw_pad, int B, int H, int W, int dtype, dd_stream stream) {
   DD_REQUIRE(dout && small && fine && wl && dsmall && dfine && dwl && H % 2 == 0 && W % 2 == 0 && dw_pad <= lddw, "dd_compose_blend_bwd: bad arguments");
+  DD_REQUIRE(dd_dtype_ok(dtype), "dd_compose_blend_bwd: bad dtype %d", dtype);
   const long total = (long)B * (H / 2) * (W / 2);
   DD_DISPATCH_DTYPE(dtype, T, hipLaunchKernelGGL(compose_blend_bwd_kernel<T>, dim3(grid_for(total)), dim3(256), 0, S(stream), dout, lddo, small, lds, fine, ldf, (const T*)wl, ldw, dsmall, ldds, accumulate_small, dfine, lddf, (T*)dwl, lddw, dw_pad, B, H, W));
   DD_LAUNCH_CHECK();
@@ -1255,6 +1269,7 @@ __global__ void compose_unpack_bwd_kernel(const T* __restrict__ dnet, int ld, fl
 extern "C" int dd_compose_unpack_bwd(const void* dnet, int ld, float* dsmall, int ldds, float* dfine, int lddf,
                                      int B, int H, int W, int dtype, dd_stream stream) {
   DD_REQUIRE(dnet && dsmall && dfine && H % 2 == 0 && W % 2 == 0 && ld >= 6, "dd_compose_unpack_bwd: bad arguments");
+  DD_REQUIRE(dd_dtype_ok(dtype), "dd_compose_unpack_bwd: bad dtype %d", dtype);
   const long total = (long)B * (H / 2) * (W / 2);
   DD_DISPATCH_DTYPE(dtype, T, hipLaunchKernelGGL(compose_unpack_bwd_kernel<T>, dim3(grid_for(total)), dim3(256), 0, S(stream), (const T*)dnet, ld, dsmall, ldds, dfine, lddf, B, H, W));
   DD_LAUNCH_CHECK();
@@ -1945,6 +1960,9 @@ __global__ void masked_add_kernel(T* __restrict__ dst, int lddst, const T* __res
 extern "C" int dd_masked_add(void* dst, int lddst, const void* src, int ldsrc, const void* mask, int ldmask, int C, long npix,
                              int accumulate, int dtype, dd_stream stream) {
   DD_REQUIRE(dst && src && C % 4 == 0 && lddst % 4 == 0 && ldsrc % 4 == 0 && (!mask || ldmask % 4 == 0), "dd_masked_add: C, ld must be multiples of 4");
+  DD_REQUIRE(dd_dtype_ok(dtype), "dd_masked_add: bad dtype %d", dtype);
+  DD_REQUIRE(vec_aligned(dst, 4 * elem_size(dtype)) && vec_aligned(src, 4 * elem_size(dtype)) && vec_aligned(mask, 4 * elem_size(dtype)),
+             "dd_masked_add: dst, src, mask must be aligned to 4 elements (%d bytes)", (int)(4 * elem_size(dtype)));
   const long total = npix * (C / 4);
   DD_DISPATCH_DTYPE(dtype, T, hipLaunchKernelGGL(masked_add_kernel<T>, dim3(grid_for(total)), dim3(256), 0, S(stream), (T*)dst, lddst, (const T*)src, ldsrc, (const T*)mask, ldmask, C, npix, accumulate));
   DD_LAUNCH_CHECK();
@@ -1988,6 +2006,9 @@ __global__ void zero_stuff_kernel(const T* __restrict__ x, int ldx, T* __restric
 }
 extern "C" int dd_zero_stuff(const void* x, int ldx, void* y, int ldy, int C, int B, int H, int W, int dtype, dd_stream stream) {
   DD_REQUIRE(x && y && C % 4 == 0 && ldx % 4 == 0 && ldy % 4 == 0, "dd_zero_stuff: C, ld must be multiples of 4");
+  DD_REQUIRE(dd_dtype_ok(dtype), "dd_zero_stuff: bad dtype %d", dtype);
+  DD_REQUIRE(vec_aligned(x, 4 * elem_size(dtype)) && vec_aligned(y, 4 * elem_size(dtype)), "dd_zero_stuff: x, y must be aligned to 4 elements (%d bytes)",
+             (int)(4 * elem_size(dtype)));
   const long total = (long)B * 4 * H * W * (C / 4);
   DD_DISPATCH_DTYPE(dtype, T, hipLaunchKernelGGL(zero_stuff_kernel<T>, dim3(grid_for(total)), dim3(256), 0, S(stream), (const T*)x, ldx, (T*)y, ldy, C, B, H, W));
   DD_LAUNCH_CHECK();
@@ -2019,6 +2040,9 @@ __global__ void space_to_depth2_kernel(const T* __restrict__ y, int ldy, T* __re
 extern "C" int dd_space_to_depth2(const void* y, int ldy, void* s, int lds, int C, int cp, int B, int H, int W, int dtype, dd_stream stream) {
   DD_REQUIRE(y && s && C > 0 && cp >= C && cp % 4 == 0 && ldy % 4 == 0 && lds % 4 == 0 && lds >= 4 * cp && ldy >= (C + 3) / 4 * 4,
              "dd_space_to_depth2: C=%d cp=%d ldy=%d lds=%d (cp, ld multiples of 4; lds >= 4 cp; the 4-channel group holding channel C - 1 readable)", C, cp, ldy, lds);
+  DD_REQUIRE(dd_dtype_ok(dtype), "dd_space_to_depth2: bad dtype %d", dtype);
+  DD_REQUIRE(vec_aligned(y, 4 * elem_size(dtype)) && vec_aligned(s, 4 * elem_size(dtype)), "dd_space_to_depth2: y, s must be aligned to 4 elements (%d bytes)",
+             (int)(4 * elem_size(dtype)));
   const long total = (long)B * H * W * cp;
   DD_DISPATCH_DTYPE(dtype, T, hipLaunchKernelGGL(space_to_depth2_kernel<T>, dim3(grid_for(total)), dim3(256), 0, S(stream), (const T*)y, ldy, (T*)s, lds, C, cp, B, H, W));
   DD_LAUNCH_CHECK();
@@ -2058,6 +2082,10 @@ __global__ void zero_unstuff_kernel(const T* __restrict__ dy, int lddy, T* __res
 extern "C" int dd_zero_unstuff(const void* dy, int lddy, void* dx, int lddx, const void* mask, int ldmask, int C, int B, int H, int W,
                                int accumulate, int dtype, dd_stream stream) {
   DD_REQUIRE(dy && dx && C % 4 == 0 && lddy % 4 == 0 && lddx % 4 == 0, "dd_zero_unstuff: C, ld must be multiples of 4");
+  DD_REQUIRE(dd_dtype_ok(dtype), "dd_zero_unstuff: bad dtype %d", dtype);
+  DD_REQUIRE(!mask || ldmask % 4 == 0, "dd_zero_unstuff: ldmask must be a multiple of 4");
+  DD_REQUIRE(vec_aligned(dy, 4 * elem_size(dtype)) && vec_aligned(dx, 4 * elem_size(dtype)) && vec_aligned(mask, 4 * elem_size(dtype)),
+             "dd_zero_unstuff: dy, dx, mask must be aligned to 4 elements (%d bytes)", (int)(4 * elem_size(dtype)));
   const long total = (long)B * H * W * (C / 4);
   DD_DISPATCH_DTYPE(dtype, T, hipLaunchKernelGGL(zero_unstuff_kernel<T>, dim3(grid_for(total)), dim3(256), 0, S(stream), (const T*)dy, lddy, (T*)dx, lddx, (const T*)mask, ldmask, C, B, H, W, accumulate));
   DD_LAUNCH_CHECK();

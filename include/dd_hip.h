@@ -215,7 +215,10 @@ int dd_colsum_segments(const void* x, int ld, int c, long rows_per_segment, int 
 
 /* ---- max pooling, TF SAME (UNet.py:42-44 3x3/s2; Tiramisu.py:55-57 2x2/s2); idx = window argmax (uint8).
  * relu_mask != 0: x is a ReLU output whose backward mask (x > 0) is folded into idx (255 = the window maximum is not positive, no
- * gradient), so dd_maxpool_bwd can be called with mask == NULL.  idx == NULL: forward only (inference), no argmax plane is stored. */
+ * gradient), so dd_maxpool_bwd can be called with mask == NULL.  idx == NULL: forward only (inference), no argmax plane is stored.
+ * idx code: a * pool + b for cell (a, b) of the window, padded cells counted; the FIRST maximum in row-major window order wins (as TF).
+ * 16-byte vectors: C and every ld multiples of 8 (bf16 / fp16) or 4 (f32), x, y, dy, dx, mask 16-byte aligned, idx 8- / 4-byte aligned;
+ * anything else returns -1 before a launch. */
 int dd_maxpool_fwd(const void* x, int ldx, void* y, int ldy, uint8_t* idx, int C, int B, int H, int W,
                    int pool, int stride, int relu_mask, int dtype, dd_stream stream);
 /* dx (+)= scatter(dy) masked by (mask>0) if mask != NULL */
@@ -721,7 +724,9 @@ int dd_frame_quality(const dd_quality_pair* pairs, int n_pairs, int H, int W, co
                      float* const* ssim_maps, void* records, void* scratch, dd_stream stream);
 
 /* ---- small helpers of the graph executor */
-/* dst (+)= src * (mask > 0)   (identity/residual gradient paths into ReLU outputs); mask may be NULL */
+/* dst (+)= src * (mask > 0)   (identity/residual gradient paths into ReLU outputs); mask may be NULL; dst == src is allowed.
+ * dd_masked_add, dd_zero_stuff, dd_zero_unstuff and dd_space_to_depth2 move 4 elements at a time: C (cp) and every ld multiples of 4, every
+ * pointer aligned to 4 elements (8 bytes bf16 / fp16, 16 bytes f32); a bad dtype code or alignment returns -1 before a launch. */
 int dd_masked_add(void* dst, int lddst, const void* src, int ldsrc, const void* mask, int ldmask, int C, long npix,
                   int accumulate, int dtype, dd_stream stream);
 /* dst[pix][0:nch] = convert(src[pix][0:nch]); dst[pix][nch:dst_pad] = 0   (dtype codes per tensor; fp32 <-> graph dtype) */

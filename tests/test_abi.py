@@ -54,7 +54,38 @@ def test_invalid_arguments_return_status_not_exception(lib):
     assert [lib.dd_loss_head_path_count(p) >= 0 for p in range(3)] == [True] * 3
     assert lib.dd_loss_head_path_count(-1) == -1 and lib.dd_loss_head_path_count(3) == -1
     assert lib.dd_maxpool_fwd(None, 8, None, 8, None, 8, 1, 8, 8, 3, 2, 1, _lib.DD_BF16, None) == -1
-
+    # the single-pass launchers of csrc/dd_pointwise.hip: a dtype code that is none of the three is refused (it used to run the fp16 kernels) ...
+    a, b, c, d, e, f, g = (ctypes.c_void_p(4096 + 256 * k) for k in range(7))      # aligned, never dereferenced
+    bad = 7
+    assert bad not in (_lib.DD_F32, _lib.DD_BF16, _lib.DD_F16)
+    for what, call in (("dd_masked_add", lambda: lib.dd_masked_add(a, 8, b, 8, c, 8, 8, 4, 0, bad, None)),
+                     ("dd_zero_stuff", lambda: lib.dd_zero_stuff(a, 8, b, 8, 8, 1, 2, 2, bad, None)),
+                     ("dd_zero_unstuff", lambda: lib.dd_zero_unstuff(a, 8, b, 8, None, 0, 8, 1, 2, 2, 0, bad, None)),
+                     ("dd_space_to_depth2", lambda: lib.dd_space_to_depth2(a, 8, b, 32, 8, 8, 1, 2, 2, bad, None)),
+                     ("dd_compose_pack", lambda: lib.dd_compose_pack(a, 3, b, 3, c, 8, 8, 1, 2, 2, bad, None)),
+                     ("dd_compose_blend_fwd", lambda: lib.dd_compose_blend_fwd(a, 3, b, 3, c, 1, d, 3, 1, 2, 2, bad, None)),
+                     ("dd_compose_blend_bwd", lambda: lib.dd_compose_blend_bwd(a, 3, b, 3, c, 3, d, 1, e, 3, 0, f, 3, g, 1, 1, 1, 2, 2, bad, None)),
+                     ("dd_compose_unpack_bwd", lambda: lib.dd_compose_unpack_bwd(a, 8, b, 3, c, 3, 1, 2, 2, bad, None)),
+                     ("dd_colsum", lambda: lib.dd_colsum(a, 8, 8, 4, b, bad, None)),
+                     ("dd_maxpool_bwd", lambda: lib.dd_maxpool_bwd(a, 8, b, c, 8, None, 0, 8, 1, 8, 8, 3, 2, 0, bad, None))):
+        assert call() == -1 and b"dtype" in lib.dd_last_error(), what
+    # ... and so is an operand that does not start on a whole vector: 16 bytes for the max-pool (idx: 8 / 4), 4 elements for the other four
+    odd16, odd8, odd4 = ctypes.c_void_p(4096 + 8), ctypes.c_void_p(4096 + 4), ctypes.c_void_p(4096 + 2)
+    for dt, idx_odd in ((_lib.DD_BF16, odd8), (_lib.DD_F32, odd4)):
+        pool = (8, 1, 8, 8, 3, 2)      # C, B, H, W, pool, stride
+        for fn, args in ((lib.dd_maxpool_fwd, (odd16, 8, b, 8, c) + pool + (1, dt, None)), (lib.dd_maxpool_fwd, (a, 8, odd16, 8, c) + pool + (1, dt, None)),
+                         (lib.dd_maxpool_fwd, (a, 8, b, 8, idx_odd) + pool + (1, dt, None)),
+                         (lib.dd_maxpool_bwd, (odd16, 8, b, c, 8, None, 0) + pool + (0, dt, None)), (lib.dd_maxpool_bwd, (a, 8, idx_odd, c, 8, None, 0) + pool + (0, dt, None)),
+                         (lib.dd_maxpool_bwd, (a, 8, b, odd16, 8, None, 0) + pool + (0, dt, None)), (lib.dd_maxpool_bwd, (a, 8, b, c, 8, odd16, 8) + pool + (0, dt, None))):
+            assert fn(*args) == -1 and b"aligned" in lib.dd_last_error(), (fn.__name__, dt)
+    for dt, odd in ((_lib.DD_BF16, odd8), (_lib.DD_F16, odd4), (_lib.DD_F32, odd16)):      # 8-byte vectors in 2-byte types, 16-byte ones in f32
+        for fn, args in ((lib.dd_masked_add, (odd, 8, b, 8, None, 0, 8, 4, 0, dt, None)), (lib.dd_masked_add, (a, 8, odd, 8, None, 0, 8, 4, 0, dt, None)),
+                         (lib.dd_masked_add, (a, 8, b, 8, odd, 8, 8, 4, 0, dt, None)),
+                         (lib.dd_zero_stuff, (odd, 8, b, 8, 8, 1, 2, 2, dt, None)), (lib.dd_zero_stuff, (a, 8, odd, 8, 8, 1, 2, 2, dt, None)),
+                         (lib.dd_zero_unstuff, (odd, 8, b, 8, None, 0, 8, 1, 2, 2, 0, dt, None)), (lib.dd_zero_unstuff, (a, 8, odd, 8, None, 0, 8, 1, 2, 2, 0, dt, None)),
+                         (lib.dd_zero_unstuff, (a, 8, b, 8, odd, 8, 8, 1, 2, 2, 0, dt, None)),
+                         (lib.dd_space_to_depth2, (odd, 8, b, 32, 8, 8, 1, 2, 2, dt, None)), (lib.dd_space_to_depth2, (a, 8, odd, 32, 8, 8, 1, 2, 2, dt, None))):
+            assert fn(*args) == -1 and b"aligned" in lib.dd_last_error(), (fn.__name__, dt)
 
 def test_struct_sizes_match_header(lib):
     # compile a tiny C program against the header and compare sizeof() of every struct with the ctypes mirror

@@ -59,6 +59,11 @@ CASES = {   # name: (environment of the child, -k expression[, test file (defaul
                                            "test_gpu_conv_fwd_ops.py"),
     "conv_fwd_ops_on_the_older_register_weight_kernels": ({"DD_CONV_RW12": "0", "DD_CONV_RW12_MASK": "0", "DD_CONV_RW8_MASK": "0", "DD_CONV_RW8": "0"},
                                                           "test_conv", "test_gpu_conv_fwd_ops.py"),
+    # the op-level pooling cases (tests/test_gpu_pointwise_ops.py) with the stride-2 specialisations of the backward off: every geometry decodes the
+    # index plane in the generic maxpool_bwd_kernel -- and its column-sum cases with the vector route off: every shape, the narrow aligned ones
+    # included, on the per-channel-lane colsum_kernel; the same float64 reference, the same bit-equal / elementwise gates
+    "pointwise_ops_maxpool_on_the_generic_backward": ({"DD_MAXPOOL_GENERIC": "1"}, "test_maxpool", "test_gpu_pointwise_ops.py"),
+    "pointwise_ops_colsum_on_the_per_channel_lane_kernel": ({"DD_COLSUM_VEC": "0"}, "test_colsum", "test_gpu_pointwise_ops.py"),
 }
 
 

@@ -488,7 +488,9 @@ def test_maxpool(eng, dtype, pool, stride, H, W, accum):
         fill(x.grad(), g0)
     g.run(g.bwd_ops)
     torch.cuda.synchronize()
-    # exact ties only happen at 0 (ReLU), where the mask kills the gradient anyway
+    # a tied maximum (zeros of the ReLU, where the mask kills the gradient anyway, but also a few equal positive values after rounding to the
+    # storage type) gives its gradient to the FIRST maximum in row-major window order, as TF and the oracle do; the rule itself
+    # is gated on tie-saturated inputs in tests/test_gpu_pointwise_ops.py
     check("dx", read(x.grad()), g0 + gx * (xv > 0), {"bf16": 4e-3 if accum else 2e-3, "f16": 5e-4 if accum else 3e-4, "f32": 1e-6}[dtype])
 
 
