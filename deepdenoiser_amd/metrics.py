@@ -4,7 +4,7 @@ The reference writes them as TensorBoard scalars every 100 steps while training 
 Training.py:246-265, 688-698, 1214) and as eval_metric_ops averaged over the validation set (add_tracked_metrics_to_dictionary,
 Training.py:283-302, 704-719, 874-877).  This module holds the host side: which metrics a configuration asks for, in the reference's order
 and under its names (metric_plan), how the per-image sums of dd_loss_metrics / dd_loss_msssim_values (include/dd_hip.h) become their values
-(metric_values), and the running mean over batches (MeanAccumulator).  The launches are Program.metrics() (program.py).
+(metric_values), and the running mean over batches (MeanAccumulator).  The launches are Program.metrics() (built in tracking.py).
 
 Histograms (the four *_histogram flags; BaseFeatureTraining.add_tracked_histograms, Training.py:267-281, written in TRAIN mode only, :679-686):
 histogram_plan lists the tags in the reference's call order, histogram_limits is TensorFlow's default bucket table, decode_histogram_records /
@@ -317,8 +317,8 @@ def histogram_values(plan, table, limits=None, out=print):
 PreviewEntry = collections.namedtuple("PreviewEntry", "name source")
 # source as in MetricEntry; name: what the tag carries (previews/<name>/image[/<k>])
 PREVIEW_PANELS = ("source", "prediction", "target", "difference")      # bit k of dd_loss_previews' panel mask
-_IMAGE_COMBINED = ("Diffuse", "Glossy", "Subsurface", "Transmission")                          # CombinedImageFeatureTraining.initialize,
-_IMAGE_SINGLE = ("Volume Direct", "Volume Indirect", "Emission", "Environment")                # Training.py:475-495
+IMAGE_COMBINED = ("Diffuse", "Glossy", "Subsurface", "Transmission")                          # CombinedImageFeatureTraining.initialize,
+IMAGE_SINGLE = ("Volume Direct", "Volume Indirect", "Emission", "Environment")                # Training.py:475-495
 
 
 def srgb_oetf(x):
@@ -346,8 +346,8 @@ def image_members(arch):
     passes (CombinedImageFeatureTraining.initialize, Training.py:475-495); None otherwise."""
     targets = {f.name for f in arch.feature_predictions if f.is_target}
     combined = {c for c, _ in combined_triples(arch)}
-    if all(c in combined for c in _IMAGE_COMBINED) and all(n in targets for n in _IMAGE_SINGLE):
-        return _IMAGE_COMBINED, _IMAGE_SINGLE
+    if all(c in combined for c in IMAGE_COMBINED) and all(n in targets for n in IMAGE_SINGLE):
+        return IMAGE_COMBINED, IMAGE_SINGLE
     return None
 
 

@@ -435,16 +435,14 @@ def main(args):
             dist.all_reduce(adds)
             dist.all_reduce(ext, op=dist.ReduceOp.MAX)
             table = M.histogram_reduce_unpack(adds.cpu().numpy(), ext.cpu().numpy(), *table["counts"].shape)
-        st = prog._histograms_built()
-        return M.histogram_values(st["plan"], table, st["limits"], out=print if rank == 0 else (lambda *a: None))
+        tracked = prog.tracking_histograms
+        return M.histogram_values(tracked.plan, table, tracked.limits, out=print if rank == 0 else (lambda *a: None))
 
     def _scalars(prog):
         table = prog.metric_table()
         if world == 1:
             return list(zip(names, prog.metric_values(table)))
-        st = prog._metrics_built()
-        n = len(st["scales"]) * st["rows"]
-        sums = torch.cat([table[:n].double().reshape(-1, B, 4).sum(dim=1).reshape(-1), table[n:].double().reshape(-1, B).sum(dim=1)])
+        sums = prog.tracking_metrics.image_sums(table)
         dist.all_reduce(sums)
         return list(zip(names, prog.metric_values(sums.cpu().numpy(), count=world * B)))
 

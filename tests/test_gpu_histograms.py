@@ -256,7 +256,7 @@ def test_program_histograms_agree_with_the_tracked_scalars():
     assert {(e.source[0], e.kind) for e in plan} == {(a, k) for a in ("feature", "combined", "image") for k in M.HISTOGRAM_KINDS[:2]} | \
         {("combined", "masked_difference")}
     assert {e.scale_index for e in plan} == {0, 1} and len(plan) == 2 * (17 * 2 + 4 * 3 + 2)
-    st = prog._metrics_built()
+    st = prog.tracking_metrics
     worst = 0.0
     for e, (tag, h) in zip(plan, histos):
         hh, ww = prog.dims[e.scale_index]
@@ -267,8 +267,8 @@ def test_program_histograms_agree_with_the_tracked_scalars():
         elif e.kind == "variation_difference":
             want = scalars[tag.replace("_variation_difference", "_variation_mean")]
         else:      # sum of difference * mask over the batch, from the metric table of that scale
-            rows = table[st["scales"].index(e.scale_index) * st["rows"]:][:st["rows"]].reshape(L.METRIC_SOURCES, B, 4)
-            want = float(rows[st["slot_of"][e.source], :, 2].astype(np.float64).sum()) / h["num"]
+            rows = table[st.scales.index(e.scale_index) * st.rows:][:st.rows].reshape(L.METRIC_SOURCES, B, 4)
+            want = float(rows[st.slot_of[e.source], :, 2].astype(np.float64).sum()) / h["num"]
             assert h["bucket"][h["bucket_limit"].index(1e-12)] >= 4 * 12 * 12 >> (2 * e.scale_index)      # the hole of _program_inputs
         err = abs(h["sum"] / h["num"] - want) / abs(want)
         worst = max(worst, err)

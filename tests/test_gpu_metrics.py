@@ -310,12 +310,12 @@ def test_program_metrics_add_up_to_the_loss(dtype):
     gate("%s: weighted metrics against loss_buf" % dtype, abs(total - loss) / abs(loss), 2e-5)
     # metrics() == the op-level call on prediction_dictionaries(), to the bit
     table = prog.metric_table().clone()
-    st = prog._metrics_built()
+    st = prog.tracking_metrics
     preds = prog.prediction_dictionaries()
     head = [f for f in arch.feature_predictions if f.is_target]
     index = {f.name: i for i, f in enumerate(head)}
     triples = M.combined_triples(arch)
-    for j, s in enumerate(st["scales"]):
+    for j, s in enumerate(st.scales):
         h, w = H >> s, W >> s
         d = L.LossDesc()
         d.n_features, d.kind, d.epsilon = len(head), KIND[tj["loss_difference"]], 1e-2
@@ -340,9 +340,9 @@ def test_program_metrics_add_up_to_the_loss(dtype):
             d.image_features[d.n_image_features] = index[nme]
             d.n_image_features += 1
         got = _run_table(d, B, h, w)
-        assert torch.equal(got, table[j * st["rows"]:(j + 1) * st["rows"]]), "scale %d" % s
+        assert torch.equal(got, table[j * st.rows:(j + 1) * st.rows]), "scale %d" % s
     # rows summed over the images (what the ranks of a data-parallel run all-reduce), with their count
-    nt = len(st["scales"]) * st["rows"]
+    nt = len(st.scales) * st.rows
     sums = torch.cat([table[:nt].double().reshape(-1, B, 4).sum(dim=1).reshape(-1), table[nt:].double().reshape(-1, B).sum(dim=1)])
     for a, b in zip(prog.metric_values(sums.cpu().numpy(), count=B), values):
         assert abs(a - b) <= 1e-12 * abs(b)

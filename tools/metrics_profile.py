@@ -53,21 +53,21 @@ def main():
         prog.set_inputs(feats, labels)
         prog.zero_grads()
         prog.forward()
-        st = prog._metrics_built()
+        tracked = prog.tracking_metrics
         stream = prog.g.stream_ptr()
         loaded = sum(1 for f in prog.head if f.load_data)
-        for op in st["launches"]:      # warm-up
+        for op in tracked.launches:      # warm-up
             op(stream)
         torch.cuda.synchronize()
         per = []
-        for j, op in enumerate(st["launches"]):
+        for j, op in enumerate(tracked.launches):
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             e0.record()
             for _ in range(args.repeats):
                 op(stream)
             e1.record()
             torch.cuda.synchronize()
-            s = st["scales"][j]
+            s = tracked.scales[j]
             nbytes = 2 * 12 * B * (H >> s) * (W >> s) * loaded
             us = 1e3 * e0.elapsed_time(e1) / args.repeats
             per.append({"scale": s, "us": us, "algorithmic_bytes": nbytes, "GB_per_s": nbytes / us * 1e-3})
@@ -84,10 +84,10 @@ def main():
             prog.metrics()
         host_us = 1e6 * (time.perf_counter() - t0) / args.repeats
         total_bytes = sum(p["algorithmic_bytes"] for p in per)
-        results[name] = {"B": B, "tile": H, "passes": len(prog.head), "loaded_passes": loaded, "metrics": len(st["plan"]), "per_scale": per,
+        results[name] = {"B": B, "tile": H, "passes": len(prog.head), "loaded_passes": loaded, "metrics": len(tracked.plan), "per_scale": per,
                          "all_scales_us": total_us, "all_scales_GB_per_s": total_bytes / total_us * 1e-3, "metrics_call_with_copy_us": host_us}
         print("%-9s B=%d %dx%d %2d passes %3d metrics: %s | all scales %.1f us (%.0f GB/s algorithmic) | metrics() incl. copy and host %.0f us" % (
-            name, B, H, W, len(prog.head), len(st["plan"]),
+            name, B, H, W, len(prog.head), len(tracked.plan),
             "  ".join("1/%d %.1f us %.0f GB/s" % (1 << p["scale"], p["us"], p["GB_per_s"]) for p in per), total_us,
             results[name]["all_scales_GB_per_s"], host_us), flush=True)
     if args.out:
