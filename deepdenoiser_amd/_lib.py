@@ -43,7 +43,7 @@ SYMBOLS = (
     "dd_compose_unpack_bwd", "dd_invert_std_fwd", "dd_invert_std_bwd", "dd_loss_head", "dd_adam_step",
     "dd_stitch", "dd_recombine", "dd_probe_tr16", "dd_masked_add", "dd_zero_stuff", "dd_zero_unstuff", "dd_convert_channels",
     "dd_augment", "dd_loss_mask_sums", "dd_crc32c", "dd_extract_tiles", "dd_compose_net_fwd", "dd_compose_net_bwd",
-    "dd_kpcn_head_fwd", "dd_kpcn_head_bwd", "dd_kpcn_head_bwd_multi", "dd_assemble_input", "dd_assemble_input_frames", "dd_conv3x3_bwd", "dd_conv3x3_bwd_multi", "dd_convt2x2_fwd", "dd_convt2x2_bwd", "dd_conv3x3_ks",
+    "dd_kpcn_head_fwd", "dd_kpcn_head_bwd", "dd_kpcn_head_bwd_multi", "dd_assemble_input", "dd_assemble_input_frames", "dd_conv3x3_bwd", "dd_conv3x3_bwd_multi", "dd_convt2x2_fwd", "dd_convt2x2_bwd", "dd_convt_bwd_wide_count", "dd_conv3x3_ks",
     "dd_conv_pw_count", "dd_wgrad_pw_count", "dd_conv_route_count", "dd_space_to_depth2", "dd_convt3_wgrad", "dd_compose_stream_plan", "dd_compose_bwd_scratch_bytes",
     "dd_loss_msssim_scratch_bytes", "dd_loss_msssim_fwd", "dd_loss_msssim_bwd", "dd_loss_msssim_values",
     "dd_loss_metrics_scratch_bytes", "dd_loss_metrics", "dd_loss_head_path_count",
@@ -63,6 +63,16 @@ def route_counts():
     """{route name: launches this process sent down it} (dd_conv_route_count)."""
     lib = load()
     return {name: lib.dd_conv_route_count(r) for r, name in enumerate(ROUTES)}
+
+
+# sub-counts behind the routes (the header's order goes on): launches already counted under a route that took a narrower instantiation
+SUBROUTES = ("rw8_k32",)
+
+
+def subroute_counts():
+    """{sub-count name: launches}: rw8_k32 = the launches of rw8_kc2 that ran conv_rw8_kernel with one K chunk."""
+    lib = load()
+    return {name: lib.dd_conv_route_count(len(ROUTES) + r) for r, name in enumerate(SUBROUTES)}
 
 
 class ConvT3WgradArgs(C.Structure):
@@ -323,6 +333,8 @@ def load():
     lib.dd_conv_pw_count.restype = C.c_long
     lib.dd_wgrad_pw_count.argtypes = []
     lib.dd_wgrad_pw_count.restype = C.c_long
+    lib.dd_convt_bwd_wide_count.argtypes = []
+    lib.dd_convt_bwd_wide_count.restype = C.c_long
     lib.dd_conv_route_count.argtypes = [i]
     lib.dd_conv_route_count.restype = C.c_long
     lib.dd_colsum.argtypes = [vp, i, i, l, vp, i, vp]

@@ -562,8 +562,19 @@ int dd_conv_rw_launch(const dd_conv_args* a, hipStream_t stream) {
     DD_ROUTE_TAKEN(DD_ROUTE_RW_6_2);
     if (a->dtype == DD_BF16) rw_launch_flags<bf16_t, 3>(p, stream); else rw_launch_flags<f16_t, 3>(p, stream);
   } else if (a->cin <= 64) {
+    // 17..32 input channels in a 32-channel weight image (the network's first 3x3 layer): ONE K chunk.  Through KC = 2 the second chunk's weight
+    // fragments are the zero vector (k0 < k_pad fails) and half of the fragment loop -- its ds_read_b128 and its MFMAs -- multiplies zeros.  The
+    // LDS image, the tiles and the DMA pieces are those of KC = 2 (RfGeo<1> == RfGeo<2>); the output is bit-identical (exact zero products
+    // added to an fp32 accumulator change nothing).  Counted under DD_ROUTE_RW8_KC2 -- same kernel template, same tiles -- and in its
+    // sub-count DD_ROUTE_RW8_K32.
+    static int on_k32 = -1;
+    if (on_k32 < 0) { const char* e = getenv("DD_CONV_RW8_K32"); on_k32 = e ? atoi(e) : 1; }
+    static_assert(RfGeo<1>::TH == RfGeo<2>::TH && RfGeo<1>::BUF == RfGeo<2>::BUF, "one K chunk: the tiles of KC = 2");
     DD_ROUTE_TAKEN(DD_ROUTE_RW8_KC2);
-    if (a->dtype == DD_BF16) rw8_launch<bf16_t, 2>(p, stream); else rw8_launch<f16_t, 2>(p, stream);
+    if (on_k32 && a->cin <= 32 && a->k_pad == 32) {
+      DD_ROUTE_TAKEN(DD_ROUTE_RW8_K32);
+      if (a->dtype == DD_BF16) rw8_launch<bf16_t, 1>(p, stream); else rw8_launch<f16_t, 1>(p, stream);
+    } else if (a->dtype == DD_BF16) rw8_launch<bf16_t, 2>(p, stream); else rw8_launch<f16_t, 2>(p, stream);
   } else if (a->mask) {
     DD_ROUTE_TAKEN(DD_ROUTE_RW8_KC4_MASK);
     if (a->dtype == DD_BF16) rw8_launch<bf16_t, 4, 8, 1>(p, stream); else rw8_launch<f16_t, 4, 8, 1>(p, stream);

@@ -189,11 +189,16 @@ template <> __device__ __forceinline__ void ct_mma_inplace<f16_t>(f32x4_t& acc, 
   asm volatile("v_mfma_f32_16x16x32_f16 %0, %1, %2, %0" : "+v"(acc) : "v"(av), "v"(bv));
 }
 
-// NSD = 64-channel slices of dy (1: C_out <= 64, tiles of 8 x 8 input pixels; 2: C_out <= 128, tiles of 8 x 4 -- the dy image stays 32 KiB)
+// NSD = 64-channel slices of dy (1: C_out <= 64, tiles of 8 x 8 input pixels; 2: 65 <= C_out <= 96, tiles of 8 x 4 -- the dy image stays 32 KiB)
+// NSD = 2 is narrowed to what 96 channels need: THREE K chunks of dy for the data gradient and THREE output-channel tiles per weight-gradient
+// wave (the full two-slice form, four of each, is 48 live registers more and spilled 11 next to the in-place MFMAs).  Its weight-gradient
+// waves take the output-channel tiles INTERLEAVED -- wave half h holds tiles h, 2 + h, 4 + h -- so that a tile's LDS slot is still an XOR of
+// compile-time bits onto a per-lane base (tile 2j + h: slot bits 2 (j & 1) + h of slice j >> 1).
 template <typename T, int NSD, bool MASK, bool ACCUM>
 __global__ __launch_bounds__(512) void convt_bwd_kernel(const CtP a) {
   extern __shared__ __attribute__((aligned(1024))) char smem[];
-  constexpr int TH = CT_T / NSD, NG = TH / 2, KC = 2 * NSD, JW = 2 * NSD, KS = TH / 4;      // tile rows, 16-pixel groups, K chunks of dx, output-channel tiles per wave of dK, K steps of dK
+  constexpr bool WIDE = NSD == 2;
+  constexpr int TH = CT_T / NSD, NG = TH / 2, KC = WIDE ? 3 : 2, JW = WIDE ? 3 : 2, KS = TH / 4;      // tile rows, 16-pixel groups, K chunks of dx, output-channel tiles per wave of dK, K steps of dK
   constexpr int Y_SLICE = CT_Y_BYTES / NSD, X_SLICE = CT_T * TH * DD_LDS_ROW, BUF = CT_Y_BYTES + 2 * X_SLICE;
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int li = lane & 15, q = lane >> 4;
@@ -229,9 +234,11 @@ __global__ __launch_bounds__(512) void convt_bwd_kernel(const CtP a) {
   const int c4 = wave * 16 + q * 4;
   T* __restrict__ DX = reinterpret_cast<T*>(a.out);
 
-  // ---- weight gradient: wave = tap tw x half h of the output channels (output-channel tiles h*JW .. h*JW + JW-1) x all 8 input-channel tiles
+  // ---- weight gradient: wave = tap tw x half h of the output channels (output-channel tiles h*JW .. h*JW + JW-1; WIDE: h, 2 + h, 4 + h) x all 8
+  // input-channel tiles
   const int tw = wave & 3, h = wave >> 2;
-  const bool w_active = h * JW * 16 < a.cout;
+  auto co_tile = [&](int j) { return WIDE ? 2 * j + h : h * JW + j; };
+  const bool w_active = co_tile(0) * 16 < a.cout;
   const int nci = (a.cin + 15) >> 4;
   unsigned yb[2], xb[2];           // transposed reads: lane (t16, gq): pixel row gq (of the 4 rows of a K step), column (t16 >> 2) [+ 4], 4-channel piece t16 & 3
   {
@@ -240,8 +247,10 @@ __global__ __launch_bounds__(512) void convt_bwd_kernel(const CtP a) {
     for (int hh = 0; hh < 2; ++hh) {
       const int col = (t16 >> 2) + 4 * hh;
       const int pd = (2 * gq + (tw >> 1)) * 16 + 2 * col + (tw & 1), px = gq * 8 + col;
-      // output-channel tile h*JW + j: slice (h*JW + j) >> 2 (NSD = 2: slice h), slot ((h*JW + j) & 3)*2 + (sub >> 1): j enters as ^ (j << 5)
-      yb[hh] = lds_base + ((h * JW) >> 2) * Y_SLICE + pd * DD_LDS_ROW + (((((h * JW) & 3) * 2 + (sub >> 1)) ^ (pd & 7)) << 4) + (sub & 1) * 8;
+      // output-channel tile h*JW + j: slot (h*JW + j)*2 + (sub >> 1) of the one slice: j enters as ^ (j << 5)
+      // WIDE, tile 2j + h: slice j >> 1, slot (2 (j & 1) + h)*2 + (sub >> 1): h is in the base, j enters as ^ ((j & 1) << 6), + (j >> 1) * Y_SLICE
+      const int slot0 = WIDE ? h * 2 : h * JW * 2;
+      yb[hh] = lds_base + pd * DD_LDS_ROW + (((slot0 + (sub >> 1)) ^ (pd & 7)) << 4) + (sub & 1) * 8;
       xb[hh] = lds_base + CT_Y_BYTES + px * DD_LDS_ROW + (((sub >> 1) ^ (px & 7)) << 4) + (sub & 1) * 8;        // input-channel tile 0; tile i: ^ ((i & 3) << 5), + (i >> 2) * slice
     }
   }
@@ -293,11 +302,15 @@ __global__ __launch_bounds__(512) void convt_bwd_kernel(const CtP a) {
     dma_tile(nxt, lds_base + (sel ^ 1) * BUF);
     const unsigned bt = sel * BUF;
     if (d_active) {
-      f32x4_t acc[NG];
+      // WIDE: output channels 0..63 (K chunks 0, 1) and 64..95 (K chunk 2) are summed apart, in the order of the two launches of the per-64 loop,
+      // and rounded below where those launches round: dx is bit for bit what the loop stores (the op-level gates take their half-ulps at
+      // exactly those rounding points; a single rounding of the whole sum leaves them by up to 1.2 gates in bf16: DESIGN 3.7)
+      f32x4_t acc[NG], acc1[WIDE ? NG : 1];
       uint2 mv[NG], oldv[NG];
 #pragma unroll
       for (int g = 0; g < NG; ++g) {
         acc[g] = f32x4_t{0.f, 0.f, 0.f, 0.f};
+        if (WIDE) acc1[g] = f32x4_t{0.f, 0.f, 0.f, 0.f};
         if (MASK) mv[g] = ct_lds8(bt + mb + g * 16 * DD_LDS_ROW);
         oldv[g] = uint2{0u, 0u};
       }
@@ -308,7 +321,8 @@ __global__ __launch_bounds__(512) void convt_bwd_kernel(const CtP a) {
 #pragma unroll
           for (int g = 0; g < NG; ++g) {
             const uint4 f = ct_lds16(bt + (db[t] ^ ((kc & 1) << 6)) + (kc >> 1) * Y_SLICE + g * 64 * DD_LDS_ROW);
-            acc[g] = mma16<T>(wf[t][kc], f, acc[g]);
+            if (WIDE && kc == 2) acc1[g] = mma16<T>(wf[t][kc], f, acc1[g]);
+            else acc[g] = mma16<T>(wf[t][kc], f, acc[g]);
           }
       if (ACCUM) {
         static_assert(NG == 4 || NG == 2, "the wait below names every request register");
@@ -336,6 +350,17 @@ __global__ __launch_bounds__(512) void convt_bwd_kernel(const CtP a) {
           o2.x = pack2<T>(f8[0] + g8[0], f8[1] + g8[1]);
           o2.y = pack2<T>(f8[2] + g8[2], f8[3] + g8[3]);
         }
+        if (WIDE) {      // the second launch of the loop: its rounded (masked) sum added to what the first one stored
+          uint2 n2;
+          n2.x = pack2<T>(acc1[g][0], acc1[g][1]);
+          n2.y = pack2<T>(acc1[g][2], acc1[g][3]);
+          if (MASK) { n2.x = mask_bf16x2(n2.x, mv[g].x); n2.y = mask_bf16x2(n2.y, mv[g].y); }
+          float f8[8], g8[8];
+          unpack8t<T>(uint4{n2.x, n2.y, 0u, 0u}, f8);
+          unpack8t<T>(uint4{o2.x, o2.y, 0u, 0u}, g8);
+          o2.x = pack2<T>(f8[0] + g8[0], f8[1] + g8[1]);
+          o2.y = pack2<T>(f8[2] + g8[2], f8[3] + g8[3]);
+        }
         if (ch_ok && ii < a.H) *reinterpret_cast<uint2*>(DX + (((long)cur.b * a.H + ii) * a.W + jj) * a.ldo + c4) = o2;
       }
     }
@@ -344,8 +369,10 @@ __global__ __launch_bounds__(512) void convt_bwd_kernel(const CtP a) {
       for (int s = 0; s < KS; ++s) {      // K step = 32 input pixels = tile rows 4s .. 4s+3  (dy rows 8s .. 8s+7: + 128 pixels)
         uint4 yf[JW];
 #pragma unroll
-        for (int j = 0; j < JW; ++j)
-          yf[j] = ct_tr_pair(bt + (yb[0] ^ (j << 5)) + s * 128 * DD_LDS_ROW, bt + (yb[1] ^ (j << 5)) + s * 128 * DD_LDS_ROW);
+        for (int j = 0; j < JW; ++j) {
+          const unsigned jx = WIDE ? (j & 1) << 6 : j << 5, jo = WIDE ? (j >> 1) * Y_SLICE : 0;      // (compile-time)
+          yf[j] = ct_tr_pair(bt + (yb[0] ^ jx) + jo + s * 128 * DD_LDS_ROW, bt + (yb[1] ^ jx) + jo + s * 128 * DD_LDS_ROW);
+        }
 #pragma unroll
         for (int i = 0; i < 8; ++i) {
           if (i >= nci) continue;
@@ -356,7 +383,7 @@ __global__ __launch_bounds__(512) void convt_bwd_kernel(const CtP a) {
         }
         if (a.db) {
 #pragma unroll
-          for (int j = 0; j < JW; ++j) {      // A fragment: 8 pixels of output channel (h*JW + j)*16 + li per lane
+          for (int j = 0; j < JW; ++j) {      // A fragment: 8 pixels of output channel co_tile(j)*16 + li per lane
             float f[8];
             unpack8t<T>(yf[j], f);
             bsum[j] += ((f[0] + f[1]) + (f[2] + f[3])) + ((f[4] + f[5]) + (f[6] + f[7]));
@@ -367,7 +394,7 @@ __global__ __launch_bounds__(512) void convt_bwd_kernel(const CtP a) {
     cur = nxt;
   }
   asm volatile("s_nop 15\n\ts_nop 15" ::: "memory");      // the last MFMAs' results (see ct_mma_inplace)
-  // flush: D[j][i] rows = output channels (h*JW + j)*16 + q*4 + e, column = input channel i*16 + li; TensorFlow layout [a][b][co][ci]
+  // flush: D[j][i] rows = output channels co_tile(j)*16 + q*4 + e, column = input channel i*16 + li; TensorFlow layout [a][b][co][ci]
   dd_det_wait();
   if (w_active) {
 #pragma unroll
@@ -378,7 +405,7 @@ __global__ __launch_bounds__(512) void convt_bwd_kernel(const CtP a) {
         if (i >= nci || ci >= a.cin) continue;
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
-          const int co = (h * JW + j) * 16 + q * 4 + e;
+          const int co = co_tile(j) * 16 + q * 4 + e;
           if (co < a.cout) atomicAdd(a.dw + ((long)tw * a.cout_total + a.co_off + co) * a.cin + ci, wacc[j][i][e]);
         }
       }
@@ -393,7 +420,7 @@ __global__ __launch_bounds__(512) void convt_bwd_kernel(const CtP a) {
         float b = bsum[j];
         b += __shfl_xor(b, 16);
         b += __shfl_xor(b, 32);
-        const int co = (h * JW + j) * 16 + li;
+        const int co = co_tile(j) * 16 + li;
         if (lane < 16 && co < a.cout) atomicAdd(a.db + a.co_off + co, b);
       }
     }
@@ -457,6 +484,9 @@ extern "C" int dd_convt2x2_fwd(const dd_convt_args* a, dd_stream stream) {
   return DD_OK;
 }
 
+static long ct_bwd_wide_launches = 0;
+extern "C" long dd_convt_bwd_wide_count(void) { return ct_bwd_wide_launches; }
+
 extern "C" int dd_convt2x2_bwd(const dd_convt_args* a, dd_stream stream) {
   CtP p;
   if (int rc = ct_fill(p, a, true)) return rc;
@@ -467,17 +497,35 @@ extern "C" int dd_convt2x2_bwd(const dd_convt_args* a, dd_stream stream) {
   p.out = a->dx; p.ldo = a->ld_dx; p.dw = a->dw; p.db = a->db; p.bias = nullptr;
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   const size_t lds = 2 * (size_t)CT_BWD_BUF;
-#define CT_BWD_N(T, N, ACC)                                                                                \
-  if (a->use_mask) { if (ACC) ct_launch(convt_bwd_kernel<T, N, true, true>, p, lds, s); else ct_launch(convt_bwd_kernel<T, N, true, false>, p, lds, s); } \
-  else { if (ACC) ct_launch(convt_bwd_kernel<T, N, false, true>, p, lds, s); else ct_launch(convt_bwd_kernel<T, N, false, false>, p, lds, s); }
-  // More than 64 output channels: one launch per block of 64 (dy is one 64-channel LDS slice per launch), the later ones accumulating into dx.
-  // (A two-slice instantiation -- NSD = 2 -- compiles but spills 11 registers next to the in-place asm MFMAs, whose results the compiler may
-  //  then store before they are written: measured wrong in f16, so it is not instantiated.)
+#define CT_BWD_N(T, N, ACC, LDS)                                                                           \
+  if (a->use_mask) { if (ACC) ct_launch(convt_bwd_kernel<T, N, true, true>, p, LDS, s); else ct_launch(convt_bwd_kernel<T, N, true, false>, p, LDS, s); } \
+  else { if (ACC) ct_launch(convt_bwd_kernel<T, N, false, true>, p, LDS, s); else ct_launch(convt_bwd_kernel<T, N, false, false>, p, LDS, s); }
+  // 65..96 output channels: ONE launch of the two-slice geometry (tiles of 8 x 4 input pixels, dy as two 64-channel LDS slices): x is read
+  // once, dx written once, the weight fragments, the first tile's DMA and the flush of fp32 atomics paid once; dx keeps the roundings of the
+  // loop below, bit for bit (DD_CONVT_BWD_WIDE=0: that loop, as for more than 96 channels).
+  static int wide_on = -1;
+  if (wide_on < 0) { const char* e = getenv("DD_CONVT_BWD_WIDE"); wide_on = e ? atoi(e) : 1; }
+  if (wide_on && a->cout > 64 && a->cout <= 96) {
+    constexpr int TH2 = CT_T / 2;
+    p.tiles_y = dd_ceil_div(a->H, TH2);
+    const long total = (long)a->B * p.tiles_x * p.tiles_y;
+    p.nwg = (int)(total < ct_cus() ? total : ct_cus());
+    const size_t lds2 = 2 * (size_t)(CT_Y_BYTES + 2 * CT_T * TH2 * DD_LDS_ROW);
+    const bool acc = a->accumulate != 0;
+    ++ct_bwd_wide_launches;
+    if (a->dtype == DD_BF16) { CT_BWD_N(bf16_t, 2, acc, lds2) } else { CT_BWD_N(f16_t, 2, acc, lds2) }
+    DD_LAUNCH_CHECK();
+    return DD_OK;
+  }
+  // More than 64 output channels otherwise: one launch per block of 64 (dy is one 64-channel LDS slice per launch), the later ones accumulating
+  // into dx (each launch rounds dx).  (The FULL two-slice instantiation -- four K chunks, four output-channel tiles per wave -- compiles but
+  // spills 11 registers next to the in-place asm MFMAs, whose results the compiler may then store before they are written: measured wrong in
+  // f16, so it is not instantiated.)
   for (int co_off = 0; co_off < a->cout; co_off += 64) {
     const int cb = a->cout - co_off < 64 ? a->cout - co_off : 64;
     p.co_off = co_off; p.cout = cb; p.coutv = (cb + 7) / 8 * 8; p.cout_total = a->cout;
     const bool acc = a->accumulate || co_off > 0;
-    if (a->dtype == DD_BF16) { CT_BWD_N(bf16_t, 1, acc) } else { CT_BWD_N(f16_t, 1, acc) }
+    if (a->dtype == DD_BF16) { CT_BWD_N(bf16_t, 1, acc, lds) } else { CT_BWD_N(f16_t, 1, acc, lds) }
   }
 #undef CT_BWD_N
   DD_LAUNCH_CHECK();

@@ -104,6 +104,8 @@ enum dd_conv_route {
   DD_ROUTE_WGRAD_REG,           /* wgrad_kernel (register-staged) */
   DD_ROUTE_WGRAD_PW,            /* wgrad_pw_kernel from dd_conv_wgrad (csrc/dd_conv_pw.hip) */
   DD_ROUTE_WGRAD_STACKED,       /* wgrad_dma_kernel, stacked dense-block form */
+  /* sub-counts: launches ALREADY counted under a route above that took a narrower instantiation of its kernel */
+  DD_ROUTE_RW8_K32,             /* of DD_ROUTE_RW8_KC2: conv_rw8_kernel<KC = 1>, 17..32 input channels in a 32-channel weight image (DD_CONV_RW8_K32=0: none) */
   DD_ROUTE_COUNT
 };
 long dd_conv_route_count(int route);
@@ -159,7 +161,7 @@ int dd_conv3x3_bwd_multi(const dd_conv_bwd_args* a, int n, dd_stream stream);
 
 /* ---- 2x2 / stride-2 transposed convolution (tf.layers.conv2d_transpose(filters, 2, strides=2), UNet.py:54-59) as streaming kernels: the
  * forward (+ bias, ReLU), and the data + weight + bias gradients of TensorFlow's autodiff (Training.py:701-702) in ONE launch.  bf16 / f16
- * storage, cin <= 128, cout a multiple of 16 (<= 96 forward, <= 128 backward: blocks of 64 run as consecutive launches).  x [B,H,W,ld_x], y / dy [B,2H,2W,ld_y];
+ * storage, cin <= 128, cout a multiple of 16 (<= 96 forward, <= 128 backward: 65..96 one launch over two 64-channel slices, more as consecutive launches over blocks of 64; dx is rounded per block of 64 either way).  x [B,H,W,ld_x], y / dy [B,2H,2W,ld_y];
  * kernel K[a][b][co][ci] (TensorFlow layout [2][2][cout][cin]):
  *   forward : y[2i+a][2j+b][co] = act(bias[co] + sum_ci x[i][j][ci] K[a][b][co][ci]);  w = dd_pack_weights layout [4*cout -> n_pad][k_pad (ci)]
  *   backward: dx[i][j][ci] = (use_mask ? x > 0 : 1) * sum_{a,b,co} dy[2i+a][2j+b][co] K[a][b][co][ci]   (accumulate: added to dx);
@@ -176,6 +178,9 @@ typedef struct {
 } dd_convt_args;
 int dd_convt2x2_fwd(const dd_convt_args* a, dd_stream stream);
 int dd_convt2x2_bwd(const dd_convt_args* a, dd_stream stream);
+/* Number of dd_convt2x2_bwd calls this process ran as ONE launch of the two-slice kernel (65 <= cout <= 96; DD_CONVT_BWD_WIDE=0: none, those
+ * layers run as two launches).  dx is bit-identical either way, so tests read the path here. */
+long dd_convt_bwd_wide_count(void);
 
 /* ---- K-streamed 3x3 convolution for deep reductions and few output channels: the dense blocks of the Tiramisu backbone
  * (tf.layers.conv2d over the growing concat, Tiramisu.py:26-41: K = 9 x up to 1 088 channels, 16 ... 128 new channels) and its 3x3 / stride-2
