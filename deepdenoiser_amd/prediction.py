@@ -14,6 +14,7 @@ import os
 import torch
 
 from . import _lib as L
+from .input_assembly import write_constant_flags
 from .naming import Naming
 from .tiling import blend_cover, blend_weights, tile_plan
 
@@ -95,8 +96,7 @@ class Predictor:
         # dictionary (Prediction.py:97-98 -> FeatureFlags.add_to_source_dictionary); they are written once here.  A caller may still
         # pass 'feature_flag/<name>' frames, which predict_frame() tiles like any other input.
         for name, buf in prog.flags_raw.items():
-            buf.zero_()
-            buf[..., self.arch.feature_flag_names.index(name)] = 1.0
+            write_constant_flags(self.arch, name, buf)
         origins = plan.windows()                                                              # row-major (Prediction.py:380-382)
         grid = [(hi, wi) for hi in range(plan.rows.count) for wi in range(plan.cols.count)]
         chunks = []
@@ -147,8 +147,7 @@ class Predictor:
         for name, buf in prog.flags_raw.items():
             key = Naming.feature_flags_name(name)
             if key not in features:      # the constant one-hot plane (Prediction.py:108): rewritten per frame, a previous caller's planes must not linger
-                buf.zero_()
-                buf[..., arch.feature_flag_names.index(name)] = 1.0
+                write_constant_flags(arch, name, buf)
             if key in features:
                 fr = torch.as_tensor(features[key], dtype=torch.float32).to(dev).contiguous()
                 if tuple(fr.shape) != (H, W, prog.flags_raw[name].shape[3]):
