@@ -50,7 +50,7 @@ SYMBOLS = (
     "dd_loss_head_dscale", "dd_loss_msssim_bwd_dscale", "dd_grads_nonfinite", "dd_adam_step_scaled", "dd_scaler_update",
     "dd_histogram_values", "dd_loss_histograms_scratch_bytes", "dd_loss_histograms", "dd_loss_previews",
     "dd_nonfinite_scan", "dd_nonfinite_repair", "dd_frame_quality_scratch_bytes", "dd_frame_quality", "dd_stitch_blend",
-    "dd_grad_norms", "dd_adam_step_clipped", "dd_adam_step_scaled_clipped",
+    "dd_grad_norms", "dd_adam_step_clipped", "dd_adam_step_scaled_clipped", "dd_sample_tiles",
 )
 
 
@@ -209,6 +209,19 @@ class AugmentDraw(C.Structure):
 
 
 AUG_PLAIN, AUG_RGB, AUG_NORMAL, AUG_SCREEN_NORMAL = 0, 1, 2, 3
+TILE_MAX_PASSES = 64      # DD_TILE_MAX_PASSES
+
+
+class TileRecord(C.Structure):         # dd_tile_record: one example of dd_sample_tiles, in device memory (64 bytes)
+    _fields_ = [("source_plane", C.c_int), ("target_plane", C.c_int), ("y0", C.c_int), ("x0", C.c_int), ("draw", AugmentDraw)]
+
+
+class TilePass(C.Structure):           # dd_tile_pass: `planes` is a device array of n_planes base pointers
+    _fields_ = [("planes", C.c_void_p), ("dst", C.c_void_p), ("C", C.c_int), ("kind", C.c_int), ("ld_dst", C.c_int), ("from_target", C.c_int)]
+
+
+class TileSamplerDesc(C.Structure):    # dd_tile_sampler_desc: a host struct, `plane_hw` is the device table [n_planes][2] of (h, w)
+    _fields_ = [("n_passes", C.c_int), ("n_planes", C.c_int), ("plane_hw", C.c_void_p), ("pass_", TilePass * TILE_MAX_PASSES)]
 
 
 class StitchEntry(C.Structure):
@@ -407,6 +420,7 @@ def load():
     lib.dd_kpcn_head_fwd.argtypes = [C.POINTER(HeadArgs), vp]
     lib.dd_kpcn_head_bwd.argtypes = [C.POINTER(HeadArgs), vp]
     lib.dd_kpcn_head_bwd_multi.argtypes = [C.POINTER(HeadArgs), i, vp]
+    lib.dd_sample_tiles.argtypes = [C.POINTER(TileSamplerDesc), vp, i, i, i, i, i, i, vp]
     _lib = lib
     return lib
 

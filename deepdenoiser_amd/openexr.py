@@ -193,6 +193,18 @@ def read_exr(path):
     return out, head
 
 
+def image_size(path):
+    """(height, width) of the file's data window from its header alone (the first 64 KiB; the whole file when the header is longer)."""
+    with open(path, "rb") as f:
+        buf = f.read(1 << 16)
+        try:
+            head, _ = _parse_header(buf)
+        except (ValueError, IndexError, struct.error):
+            head, _ = _parse_header(buf + f.read())
+    x0, y0, x1, y1 = head["data_window"]
+    return y1 - y0 + 1, x1 - x0 + 1
+
+
 def read_image(path):
     """What OpenEXRDirectory._load_exr returns (OpenEXRDirectory.py:125-151): float32 [H,W,3] in R,G,B order.  Channel names may carry a
     layer prefix ("ViewLayer.Combined.R"); a file with a single channel (Alpha, Depth written as Y / A / Z / V) is replicated to 3."""

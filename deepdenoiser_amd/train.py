@@ -23,7 +23,14 @@ its staged mini-batch as source | prediction | target [| difference, `--image_di
 (metrics.preview_plan), on the device from the pre-step forward (shared with the tracked scalars when both fall on one step), and writes them
 as ONE event of their own that holds only the images.  Every validation pass then also writes the previews of the first examples of each
 validation set's first mini-batch into that set's eval_<name> event file at the global step: that stream is not shuffled, so the same
-tiles appear every epoch.  No collective: the other ranks do nothing.  Not reproduced: histograms of weights or gradients."""
+tiles appear every epoch.  No collective: the other ranks do nothing.  Not reproduced: histograms of weights or gradients.
+
+Frames on the device (new: the reference trains from tile records only): with `--frames tfrecords.json` (or "frames" in Training.json) the
+rendered EXRs the TFRecords-JSON names are decoded once and kept as fp32 planes in device memory (frame_bank.py); base_tfrecords_directory is
+not read and no .tfrecords file is needed.  A mini-batch is then B records (plane, origin, augmentation draw) and ONE dd_sample_tiles launch
+that crops and augments every pass into the program's input and target buffers; TileStream, Uploader and DataAugmentation.apply are not
+used.  `--frames_crops random` cuts the tiles anywhere in a frame, `grid` on the fixed grid of the tile sets; an epoch has as many examples
+as the grid in either mode.  Validation runs over the grid of the JSON's validation mode, without augmentation."""
 import argparse
 import json
 import multiprocessing
@@ -78,6 +85,16 @@ def parser():
                    help="Every --summary_steps steps also write gradient_norm/<variable> and weight_norm/<variable> of every variable and "
                         "gradient_nonfinite_variables (the global gradient_norm and gradient_clip_coefficient are written whenever this or "
                         "clipping is on).")
+    p.add_argument("--frames", default=None, metavar="PATH",
+                   help="Train from rendered EXR frames kept in device memory instead of .tfrecords tiles: the TFRecords-JSON (the schema of "
+                        "TFRecordsExample.json) that names the scene directories.  Overrides the optional \"frames\" of Training.json; "
+                        "base_tfrecords_directory is then not read.")
+    p.add_argument("--frames_spp", type=int, default=None, help="Samples per pixel of the source renderings (default: the first of source.samples_per_pixel).")
+    p.add_argument("--frames_crops", default="random", choices=["random", "grid"],
+                   help="Where the tiles of a mini-batch are cut: anywhere in a frame, or on the fixed grid of the .tfrecords tile sets "
+                        "(shuffled per epoch).  An epoch has as many examples as the grid in either mode.")
+    p.add_argument("--frame_memory_gb", type=float, default=None,
+                   help="The most device memory the frames may take (default: 80 %% of what is free when they are loaded).")
     p.add_argument("--seed", type=int, default=0, help="seed of the file / example shuffles and of the source index tuples (shared by all ranks)")
     return p
 
@@ -290,12 +307,52 @@ def preview_summaries(prog, table, preview):
     return [summaries.image_summary(tag, a) for tag, a in prog.preview_images(table, preview["images"], preview["which"])]
 
 
+def _evaluate_set(trainer, arch, stem, feeds, tail, B, rank, world, plan, metrics_out, previews_out, preview, printed=None):
+    """One validation set.  `feeds` yields once per mini-batch of this rank, AFTER it has put that mini-batch into the program's input
+    buffers; tail() -> (padded, real_in_last, decoded) once it is exhausted.  Returns (stem, mean loss, examples) or None for an empty set."""
+    import torch.distributed as dist
+    total = torch.zeros(2, dtype=torch.float64, device=arch.device)
+    losses, tables = [], []
+    for _ in feeds:
+        trainer.program.zero_grads()
+        trainer.program.forward()
+        losses.append(trainer.program.loss_buf.double().sum())
+        if plan:      # (a copy on the device: how many of the LAST mini-batch are real is known only when the stream has ended)
+            tables.append(trainer.program.metric_table().clone())
+        if previews_out is not None and preview is not None and len(losses) == 1:
+            previews_out[stem] = preview_summaries(trainer.program, trainer.program.preview_table(**preview), preview)
+    padded, real_in_last, decoded = tail()
+    # every example counts once: a mini-batch's mean is weighed by its REAL examples (the last round of the epoch is filled with repeats)
+    for i, l in enumerate(losses):
+        w = real_in_last if (padded and i == len(losses) - 1) else B
+        total[0] += l * w
+        total[1] += w
+    if world > 1:
+        dist.all_reduce(total)
+    if plan:
+        acc = MeanAccumulator(len(plan))
+        for i, t in enumerate(tables):
+            w = real_in_last if (padded and i == len(tables) - 1) else B
+            if w > 0:      # repeated examples do not count
+                acc.add(trainer.program.metric_values(t, real=w), w)
+        if world > 1:
+            state = torch.from_numpy(acc.state()).to(arch.device)
+            dist.all_reduce(state)
+            acc.from_state(state.cpu().numpy())
+        if acc.weight > 0:
+            metrics_out[stem] = list(zip([e.name for e in plan], acc.result()))
+    if float(total[1]) > 0:
+        if padded and rank == 0:
+            print("validation set %s: the last round was filled up with %d repeated example(s) (%d decoded)" % (printed or stem, padded, decoded))
+        return stem, float(total[0] / total[1]), int(total[1])
+    return None
+
+
 def run_validation(trainer, arch, tj, base, B, rank, world, threads, metrics_out=None, previews_out=None, preview=None):
     """Training.py:1230-1250 / :1264-1284: every validation*.json, tiles of base/validation/<spp>/, no augmentation, mean loss.
     metrics_out: a dict that receives {validation json stem: [(metric name, mean over the set)]} -- the tracked metrics of every mini-batch
     (program.metrics over its real examples), averaged with the weights the loss gets.  previews_out (with `preview`, preview_settings): a
     dict that receives {stem: image summaries of the first examples of the set's first mini-batch} -- on the rank that passes it only."""
-    import torch.distributed as dist
     results = []
     plan = trainer.program.metric_plan() if metrics_out is not None else []
     for name in evaluation_jsons(base, "validation"):
@@ -310,41 +367,38 @@ def run_validation(trainer, arch, tj, base, B, rank, world, threads, metrics_out
             print("validation set %s: tiles of %d pixels, the program was built for %d -- skipped" % (name, st["tiles_height_width"], trainer.program.H))
             continue
         stream = TileStream(vdir, "validation", arch, B, st["tiles_height_width"], spp, tuples, rank, world, rng=None, threads=threads, pad_last=True)
-        total = torch.zeros(2, dtype=torch.float64, device=arch.device)
-        losses, tables = [], []
-        for feats, labels in stream:
-            trainer.program.set_inputs({k: v.to(arch.device) for k, v in feats.items()}, {k: v.to(arch.device) for k, v in labels.items()})
-            trainer.program.zero_grads()
-            trainer.program.forward()
-            losses.append(trainer.program.loss_buf.double().sum())
-            if plan:      # (a copy on the device: how many of the LAST mini-batch are real is known only when the stream has ended)
-                tables.append(trainer.program.metric_table().clone())
-            if previews_out is not None and preview is not None and len(losses) == 1:
-                previews_out[os.path.splitext(name)[0]] = preview_summaries(trainer.program, trainer.program.preview_table(**preview), preview)
-        # every example counts once: a mini-batch's mean is weighed by its REAL examples (the last round of the epoch is filled with repeats)
-        for i, l in enumerate(losses):
-            w = stream.real_in_last if (stream.padded and i == len(losses) - 1) else B
-            total[0] += l * w
-            total[1] += w
-        if world > 1:
-            dist.all_reduce(total)
-        if plan:
-            acc = MeanAccumulator(len(plan))
-            for i, t in enumerate(tables):
-                w = stream.real_in_last if (stream.padded and i == len(tables) - 1) else B
-                if w > 0:      # repeated examples do not count
-                    acc.add(trainer.program.metric_values(t, real=w), w)
-            if world > 1:
-                state = torch.from_numpy(acc.state()).to(arch.device)
-                dist.all_reduce(state)
-                acc.from_state(state.cpu().numpy())
-            if acc.weight > 0:
-                metrics_out[os.path.splitext(name)[0]] = list(zip([e.name for e in plan], acc.result()))
-        if float(total[1]) > 0:
-            results.append((os.path.splitext(name)[0], float(total[0] / total[1]), int(total[1])))
-            if stream.padded and rank == 0:
-                print("validation set %s: the last round was filled up with %d repeated example(s) (%d decoded)" % (name, stream.padded, stream.decoded))
+
+        def feeds(stream=stream):
+            for feats, labels in stream:
+                trainer.program.set_inputs({k: v.to(arch.device) for k, v in feats.items()}, {k: v.to(arch.device) for k, v in labels.items()})
+                yield
+        got = _evaluate_set(trainer, arch, os.path.splitext(name)[0], feeds(), lambda: (stream.padded, stream.real_in_last, stream.decoded), B, rank,
+                            world, plan, metrics_out, previews_out, preview, printed=name)
+        if got is not None:
+            results.append(got)
     return results
+
+
+def run_validation_frames(trainer, arch, tj, sampler, B, rank, world, metrics_out=None, previews_out=None, preview=None, stem="validation"):
+    """The validation pass of a --frames run: the grid records of the validation frames (frame_bank.TileSampler.grid_records), no
+    augmentation; the last round is filled up by cycling over its own examples and weighed by the real ones, as run_validation does."""
+    plan = trainer.program.metric_plan() if metrics_out is not None else []
+    tuples, _ = source_index_tuples(sampler.bank.S, tj["number_of_source_index_tuples"], arch.number_of_sources_per_target, rng=random.Random(0))
+    records = sampler.grid_records(tuples)
+    need, count = B * world, len(records)
+    left = count % need
+    padded, real_in_last = 0, B
+    if left:
+        tail = records[count - left:]
+        records = np.concatenate([records, tail[np.arange(need - left) % left]])
+        padded, real_in_last = need - left, max(0, min(B, left - rank * B))
+
+    def feeds():
+        for r0 in range(0, len(records), need):
+            sampler.sample(records[r0 + rank * B:r0 + (rank + 1) * B])
+            yield
+    got = _evaluate_set(trainer, arch, stem, feeds(), lambda: (padded, real_in_last, count), B, rank, world, plan, metrics_out, previews_out, preview)
+    return [got] if got is not None else []
 
 
 def main(args):
@@ -360,10 +414,20 @@ def main(args):
     arch = Architecture(aj, source_data_format="channels_last", data_format=args.data_format, device="cuda:%d" % local, dtype=args.dtype,
                         loss_scale=args.loss_scale, clip_norm=grad_clip.resolve_clip_norm(args.clip_norm, tj),
                         track_gradient_norms=args.gradient_norms)
-    base = tj["base_tfrecords_directory"] if os.path.isabs(tj["base_tfrecords_directory"]) else os.path.join(directory, tj["base_tfrecords_directory"])
     if "training" not in tj["modes"]:
         raise Exception("No training mode found.")
-    st = tfrecords.read_settings(base, "training")
+    frames_json = args.frames
+    if frames_json is None and tj.get("frames"):
+        frames_json = tj["frames"] if os.path.isabs(tj["frames"]) else os.path.join(directory, tj["frames"])
+    base = frame_set = None
+    if frames_json is not None:      # frames kept on the device (frame_bank.py): no .tfrecords, base_tfrecords_directory is not read
+        from .frame_bank import FrameBank, FrameSet, TileSampler
+        frame_set = FrameSet.from_json(frames_json, "training", log=print if rank == 0 else (lambda *a: None))
+        st = {"tiles_height_width": frame_set.tile, "number_of_sources_per_example": frame_set.number_of_sources_per_example,
+              "source_samples_per_pixel_list": [frame_set.source_spps[0] if args.frames_spp is None else args.frames_spp]}
+    else:
+        base = tj["base_tfrecords_directory"] if os.path.isabs(tj["base_tfrecords_directory"]) else os.path.join(directory, tj["base_tfrecords_directory"])
+        st = tfrecords.read_settings(base, "training")
     spp = st["source_samples_per_pixel_list"][0]
     B, tile = tj["batch_size"], st["tiles_height_width"]
     trainer = Trainer(arch, tj, B, tile, tile, world_size=world)
@@ -374,6 +438,27 @@ def main(args):
         step = tf_checkpoint.load_variables(arch, latest)["global_step"]
         print("restored %s (global_step %d)" % (latest, step))
     validate = "validation" in tj["modes"]
+    usage = DataAugmentationUsage.from_training_json(tj)
+    sampler = validation_sampler = None
+    if frame_set is not None:
+        quiet = print if rank == 0 else (lambda *a: None)
+        limit = None if args.frame_memory_gb is None else int(args.frame_memory_gb * 2 ** 30)
+        threads = max(1, min(args.threads, 8))      # EXR decoders: a small fixed cap, whatever the host has
+
+        def resident(mode, frames):
+            bank = FrameBank(arch, frames, spp, arch.device, limit, threads=threads, log=quiet)
+            quiet("frames: %s -- %d scene(s), %d planes, %.3f GB on the device (%d spp, tiles of %d)"
+                  % (mode, len(bank.scenes), bank.n_planes, bank.total_bytes / 1e9, bank.spp, bank.tile))
+            return TileSampler(trainer.program, bank, usage)
+        if not args.validate:
+            sampler = resident("training", frame_set)
+        with open(frames_json, encoding="utf-8") as f:
+            validate = validate and "validation" in json.load(f)["modes"]
+        if validate or args.validate:
+            validation_set = FrameSet.from_json(frames_json, "validation", log=quiet)
+            if validation_set.tile != tile:
+                raise ValueError("validation tiles of %d pixels, training tiles of %d" % (validation_set.tile, tile))
+            validation_sampler = resident("validation", validation_set)
 
     eval_writers = {}
 
@@ -381,8 +466,11 @@ def main(args):
 
     def report_validation(tag):
         tracked, shown = {}, ({} if (preview is not None and rank == 0) else None)
-        for name, loss, n in run_validation(trainer, arch, tj, base, B, rank, world, args.threads, metrics_out=tracked, previews_out=shown,
-                                            preview=preview):
+        if validation_sampler is not None:
+            results = run_validation_frames(trainer, arch, tj, validation_sampler, B, rank, world, metrics_out=tracked, previews_out=shown, preview=preview)
+        else:
+            results = run_validation(trainer, arch, tj, base, B, rank, world, args.threads, metrics_out=tracked, previews_out=shown, preview=preview)
+        for name, loss, n in results:
             if rank == 0:
                 print("%s: %s loss %.5f over %d batches" % (tag, name, loss, n))
                 for metric, value in tracked.get(name, []):
@@ -446,21 +534,15 @@ def main(args):
         dist.all_reduce(sums)
         return list(zip(names, prog.metric_values(sums.cpu().numpy(), count=world * B)))
 
-    usage = DataAugmentationUsage.from_training_json(tj)
     gen = torch.Generator().manual_seed(1234 + rank)
-    uploader = Uploader(arch.device)
+    uploader = Uploader(arch.device) if sampler is None else None
     main_stream = torch.cuda.current_stream()
-    for epoch in range(args.train_epochs):
-        rng = random.Random(args.seed * 1000003 + epoch)                 # shared by the ranks: same files, same shuffle, same index tuples
-        tuples, _ = source_index_tuples(st["number_of_sources_per_example"], tj["number_of_source_index_tuples"], arch.number_of_sources_per_target,
-                                        rng=rng)                         # redrawn every epoch (Training.py:1258)
-        stream = TileStream(os.path.join(base, "training"), "training", arch, B, tile, spp, tuples, rank, world, rng=rng, threads=args.threads)
-        total, count, t0, steps0 = 0.0, 0, time.time(), step
-        staged = None
+
+    def tfrecords_steps(stream):
+        """Puts one mini-batch after the other into the program's input buffers; yields whether it was the epoch's last."""
         it = iter(stream)
         nxt = next(it, None)
-        if nxt is not None:
-            staged = uploader.stage(*nxt)
+        staged = uploader.stage(*nxt) if nxt is not None else None
         while staged is not None:
             feats, labels, done, keep = staged
             main_stream.wait_event(done)
@@ -470,6 +552,29 @@ def main(args):
             trainer.program.set_inputs(feats, labels)
             nxt = next(it, None)                                         # the next mini-batch uploads while this step runs
             staged = uploader.stage(*nxt) if nxt is not None else None
+            yield staged is None
+
+    def frames_steps(rng, tuples):
+        """The same from resident frames: B records and B draws, one upload of a few KB and one launch per mini-batch (frame_bank.py)."""
+        sampler.reset()
+        records = sampler.draw(rng, args.frames_crops, tuples, rank, world)
+        while records is not None:
+            sampler.sample(records, DataAugmentation.draw(B, gen))
+            records = sampler.draw(rng, args.frames_crops, tuples, rank, world)
+            yield records is None
+
+    for epoch in range(args.train_epochs):
+        rng = random.Random(args.seed * 1000003 + epoch)                 # shared by the ranks: same files, same shuffle, same index tuples
+        tuples, _ = source_index_tuples(st["number_of_sources_per_example"], tj["number_of_source_index_tuples"], arch.number_of_sources_per_target,
+                                        rng=rng)                         # redrawn every epoch (Training.py:1258)
+        if sampler is None:
+            stream = TileStream(os.path.join(base, "training"), "training", arch, B, tile, spp, tuples, rank, world, rng=rng, threads=args.threads)
+            steps = tfrecords_steps(stream)
+        else:
+            stream = None
+            steps = frames_steps(rng, tuples)
+        total, count, t0, steps0 = 0.0, 0, time.time(), step
+        for last in steps:
             summary = args.summary_steps > 0 and (step + 1) % args.summary_steps == 0
             # image summaries: rank 0 alone, launched on the pre-step forward (made here, shared with the tracked scalars), read back behind
             # the step like the histogram records
@@ -500,16 +605,17 @@ def main(args):
                         writer.add_summaries(step, head, histos, scalars)
                     else:
                         writer.add_scalars(step, head + scalars)
-            if step % 50 == 0 or staged is None:
+            if step % 50 == 0 or last:
                 total, count = total + float(loss), count + 1
         if dist is not None:
             dist.barrier()
         if rank == 0:
             dt = max(time.time() - t0, 1e-9)
             skipped = (trainer.program.sync_adam_step() or {}).get("skipped_total", 0)
-            print("epoch %d: global_step %d, loss %.5f (%d steps, %.1f tiles/s, %d examples decoded)%s" % (
-                epoch + 1, step, total / max(count, 1), step - steps0, (step - steps0) * B * world / dt, stream.decoded,
-                ", %d steps skipped so far (loss scale)" % skipped if skipped else ""))
+            print("epoch %d: global_step %d, loss %.5f (%d steps, %.1f tiles/s, %d examples %s)%s" % (
+                epoch + 1, step, total / max(count, 1), step - steps0, (step - steps0) * B * world / dt,
+                stream.decoded if stream is not None else (step - steps0) * B * world,
+                "decoded" if stream is not None else "cut from resident frames", ", %d steps skipped so far (loss scale)" % skipped if skipped else ""))
             tf_checkpoint.save_variables(arch, model_dir, global_step=step)
         if dist is not None:
             dist.barrier()                                               # nobody runs ahead of the checkpoint

@@ -748,6 +748,30 @@ enum { DD_AUG_PLAIN = 0, DD_AUG_RGB = 1, DD_AUG_NORMAL = 2, DD_AUG_SCREEN_NORMAL
 int dd_augment(const float* src, float* dst, int C, int B, int H, int W, const dd_augment_draw* draws, int kind,
                int use_flip, int use_rotate, int use_permute, int use_normal_rotation, dd_stream stream);
 
+/* ---- training tiles cut from frames that stay in device memory (csrc/dd_tile_sampler.hip).  Replaces the tile set the reference writes
+ * to disk (TFRecordsCreator.py:125-133: the fixed grid of non-overlapping tiles; :221-231: one record per tile), its decode
+ * (Training.py:507-524) and the per-pass augmentation launches (Training.py:794-821): ONE launch fills every input and target tile buffer of
+ * a mini-batch,
+ *     dst[b, y, x, 0:C] = augment(plane[y0 : y0 + T, x0 : x0 + T, :])[y, x, :]
+ * with `augment` exactly dd_augment's for the pass's kind, the record's draw and the four use_* switches.  Channels C .. ld_dst-1 of dst are
+ * not written.
+ *   plane   : one rendering of one scene.  Every pass has a DEVICE array of n_planes base pointers (fp32 [h, w, C], contiguous; NULL where the
+ *             pass is not loaded for that rendering: such a block writes nothing); plane_hw is the DEVICE table [n_planes][2] of (h, w),
+ *             shared by all passes (scenes differ in size).
+ *   record  : DEVICE, one per example: the plane the source passes read, the plane the target passes read, the window's origin, the draw.
+ *             Records cannot be checked on the host; the kernel clamps the plane index into 0 .. n_planes-1 and the origin into
+ *             [0, h-T] x [0, w-T] (a plane smaller than a tile is skipped), so a bad record reads no byte outside a plane.
+ *   pass    : C in {1, 3}; kind DD_AUG_*; dst fp32 [B, T, T, ld_dst], ld_dst >= C; from_target: reads the record's target plane.
+ * desc is a HOST struct (copied by value).  Refused with a negative status and no launch: NULL pointers, n_passes outside
+ * 1 .. DD_TILE_MAX_PASSES, C outside {1, 3}, a kind other than DD_AUG_PLAIN with C != 3, ld_dst < C, use_flip with a DD_AUG_NORMAL pass (as
+ * dd_augment), T < 1, B < 1.  No host sync. */
+#define DD_TILE_MAX_PASSES 64
+typedef struct { int source_plane; int target_plane; int y0; int x0; dd_augment_draw draw; } dd_tile_record;
+typedef struct { const float* const* planes; float* dst; int C; int kind; int ld_dst; int from_target; } dd_tile_pass;
+typedef struct { int n_passes; int n_planes; const int* plane_hw; dd_tile_pass pass[DD_TILE_MAX_PASSES]; } dd_tile_sampler_desc;
+int dd_sample_tiles(const dd_tile_sampler_desc* desc, const dd_tile_record* records, int B, int T, int use_flip, int use_rotate,
+                    int use_permute, int use_normal_rotation, dd_stream stream);
+
 /* 3x3/s2 transpose conv (Tiramisu.py:62-64) = 3x3 SAME conv of the zero-stuffed input with the flipped kernel:
  * y[B,2H,2W,C] = 0 except y[2i+1,2j+1] = x[i,j]; and its adjoint dx[i,j] (+)= dy[2i+1,2j+1] * (mask>0). */
 int dd_zero_stuff(const void* x, int ldx, void* y, int ldy, int C, int B, int H, int W, int dtype, dd_stream stream);
