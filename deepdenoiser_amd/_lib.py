@@ -51,6 +51,7 @@ SYMBOLS = (
     "dd_histogram_values", "dd_loss_histograms_scratch_bytes", "dd_loss_histograms", "dd_loss_previews",
     "dd_nonfinite_scan", "dd_nonfinite_repair", "dd_frame_quality_scratch_bytes", "dd_frame_quality", "dd_stitch_blend",
     "dd_grad_norms", "dd_adam_step_clipped", "dd_adam_step_scaled_clipped", "dd_sample_tiles",
+    "dd_tile_statistics",
 )
 
 
@@ -222,6 +223,25 @@ class TilePass(C.Structure):           # dd_tile_pass: `planes` is a device arra
 
 class TileSamplerDesc(C.Structure):    # dd_tile_sampler_desc: a host struct, `plane_hw` is the device table [n_planes][2] of (h, w)
     _fields_ = [("n_passes", C.c_int), ("n_planes", C.c_int), ("plane_hw", C.c_void_p), ("pass_", TilePass * TILE_MAX_PASSES)]
+
+
+STAT_MAX_PASSES = 64      # DD_STAT_MAX_PASSES
+# the fields of a dd_tile_statistics row, in the order of the header's enum (DD_STAT_*)
+STAT_FIELD_NAMES = ("present", "min", "max", "min_log1p", "max_log1p", "pivot", "pivot_log1p", "sum", "sum_sq", "sum_log1p", "sum_sq_log1p",
+                    "count", "mask_sum", "masked_sum", "masked_sum_sq", "masked_sum_log1p", "masked_sum_sq_log1p")
+STAT_FIELDS = len(STAT_FIELD_NAMES)      # DD_STAT_FIELDS
+
+
+class StatWindow(C.Structure):         # dd_stat_window: one window of dd_tile_statistics, in device memory (16 bytes)
+    _fields_ = [("plane", C.c_int), ("mask_plane", C.c_int), ("y0", C.c_int), ("x0", C.c_int)]
+
+
+class StatPass(C.Structure):           # dd_stat_pass: `planes` / `mask_planes` are device arrays of n_planes base pointers (mask_planes may be NULL)
+    _fields_ = [("planes", C.c_void_p), ("mask_planes", C.c_void_p), ("C", C.c_int), ("is_alpha", C.c_int)]
+
+
+class StatDesc(C.Structure):           # dd_stat_desc: a host struct, `plane_hw` is the device table [n_planes][2] of (h, w)
+    _fields_ = [("n_passes", C.c_int), ("n_planes", C.c_int), ("plane_hw", C.c_void_p), ("pass_", StatPass * STAT_MAX_PASSES)]
 
 
 class StitchEntry(C.Structure):
@@ -421,6 +441,7 @@ def load():
     lib.dd_kpcn_head_bwd.argtypes = [C.POINTER(HeadArgs), vp]
     lib.dd_kpcn_head_bwd_multi.argtypes = [C.POINTER(HeadArgs), i, vp]
     lib.dd_sample_tiles.argtypes = [C.POINTER(TileSamplerDesc), vp, i, i, i, i, i, i, vp]
+    lib.dd_tile_statistics.argtypes = [C.POINTER(StatDesc), vp, i, i, vp, vp]
     _lib = lib
     return lib
 

@@ -6,6 +6,7 @@ TensorFlow 1.x and OpenCV).  Here the EXRs themselves are the data set:
     FrameSet     the TFRecords-JSON (TFRecordsExample.json) and the scene directories it names: which renderings exist, which are usable
                  (OpenEXRDirectories.py:18-29, OpenEXRDirectory.py:20, TFRecordsCreator.py:62-88); host only, reads EXR headers only
     FrameBank    the passes an architecture loads, of one samples-per-pixel count, decoded once and kept as fp32 planes on the device
+                 (FrameBank.for_passes: a given set of passes, of one or several counts, without an architecture -- statistics.py)
     TileSampler  a mini-batch = B windows of resident planes: `draw` picks them (random crops, or the reference's fixed grid of
                  TFRecordsCreator.py:125-133), `sample` uploads the B records and makes ONE dd_sample_tiles launch that crops and augments
                  every pass into the program's input and target buffers (csrc/dd_tile_sampler.hip)
@@ -140,25 +141,50 @@ class FrameBank:
         self.device = torch.device(arch.device if device is None else device)
         if self.spp not in frame_set.source_spps:
             raise ValueError("%d samples per pixel: the frame set lists %s" % (self.spp, frame_set.source_spps))
+        self.spps = [self.spp]
         self._channels(arch)
         for what, need, have in (("source", self.source_channels, frame_set.source_passes), ("target", self.target_channels, frame_set.target_passes)):
             for name in need:
                 if name not in have:
                     raise ValueError("the architecture loads the %s pass '%s', which the frame set's %s features do not list" % (what, name, what))
+        self._load(frame_set.scenes, memory_limit_bytes, threads, log)
+        if not self.scenes:
+            raise ValueError("no usable scene is left (%d skipped)" % (len(frame_set.skipped) + len(self.skipped)))
+        self._tables()
+
+    @classmethod
+    def for_passes(cls, frame_set, source_channels, target_channels, spp, scenes=None, device="cuda", memory_limit_bytes=None, threads=4, log=print):
+        """A bank of the passes `source_channels` / `target_channels` ({pass name: channels}) without an Architecture: what the data-set
+        statistics read (deepdenoiser_amd/statistics.py).  `spp`: one samples-per-pixel count or a list of them -- with a list a scene owns
+        len(spp) * S source planes, those of the first count first, and `S` is that product, so source_plane / target_plane hold.  `scenes`:
+        the scenes of `frame_set` to load (all of them when None).  A bank whose scenes were all skipped has no plane and is not refused."""
+        self = cls.__new__(cls)
+        self.frame_set, self.tile, self.device = frame_set, frame_set.tile, torch.device(device)
+        self.spps = [int(s) for s in (spp if isinstance(spp, (list, tuple)) else [spp])]
+        for s in self.spps:
+            if s not in frame_set.source_spps:
+                raise ValueError("%d samples per pixel: the frame set lists %s" % (s, frame_set.source_spps))
+        self.spp, self.S = self.spps[0], frame_set.number_of_sources_per_example * len(self.spps)
+        self.source_channels, self.target_channels = dict(source_channels), dict(target_channels)
+        self._load(frame_set.scenes if scenes is None else scenes, memory_limit_bytes, threads, log)
+        self._tables()
+        return self
+
+    def _load(self, scenes, memory_limit_bytes, threads, log):
         # ---- the bytes, before anything is allocated
         per_pixel = 4 * (self.S * sum(self.source_channels.values()) + sum(self.target_channels.values()))
-        self.total_bytes = sum(s.height * s.width * per_pixel for s in frame_set.scenes)
+        self.total_bytes = sum(s.height * s.width * per_pixel for s in scenes)
         if memory_limit_bytes is None:
             memory_limit_bytes = int(0.8 * torch.cuda.mem_get_info(self.device)[0]) if self.device.type == "cuda" else None
         if memory_limit_bytes is not None and self.total_bytes > memory_limit_bytes:
             raise MemoryError("the frames take %d bytes of device memory (%d scenes, %d source renderings each, %d spp), the limit is %d bytes"
-                              % (self.total_bytes, len(frame_set.scenes), self.S, self.spp, memory_limit_bytes))
+                              % (self.total_bytes, len(scenes), self.S, self.spp, memory_limit_bytes))
         # ---- decode and upload, scene by scene
         self.threads = max(1, min(int(threads), 32))
         self.scenes, self.hw, self.skipped = [], [], []
         self.planes = {name: [] for name in set(self.source_channels) | set(self.target_channels)}
         with concurrent.futures.ThreadPoolExecutor(max_workers=self.threads) as pool:
-            for scene in frame_set.scenes:
+            for scene in scenes:
                 try:
                     loaded = self._load_scene(scene, pool)
                 except openexr.ExrError as e:
@@ -170,9 +196,6 @@ class FrameBank:
                     self.hw.append((scene.height, scene.width))
                     for name in self.planes:
                         self.planes[name].append(plane.get(name))
-        if not self.scenes:
-            raise ValueError("no usable scene is left (%d skipped)" % (len(frame_set.skipped) + len(self.skipped)))
-        self._tables()
 
     def _channels(self, arch):
         features = arch.feature_predictions + arch.auxiliary_features
@@ -216,8 +239,9 @@ class FrameBank:
             if not np.isfinite(image).all():
                 raise openexr.ExrError("there is at least one value in %s which is not finite" % path)
             return np.ascontiguousarray(image, dtype=np.float32)
-        jobs = [(p, name, pool.submit(load, r, name, ch)) for p, r in enumerate(scene.sources[self.spp]) for name, ch in self.source_channels.items()]
-        same = scene.target in scene.sources[self.spp]        # ("best" may be the source spp itself: the rendering is decoded once)
+        renderings = [r for spp in self.spps for r in scene.sources[spp]]
+        jobs = [(p, name, pool.submit(load, r, name, ch)) for p, r in enumerate(renderings) for name, ch in self.source_channels.items()]
+        same = scene.target in renderings                     # ("best" may be the source spp itself: the rendering is decoded once)
         if not same:
             jobs += [(self.S, name, pool.submit(load, scene.target, name, ch)) for name, ch in self.target_channels.items()]
         planes = [{} for _ in range(self.S + 1)]
@@ -230,7 +254,7 @@ class FrameBank:
         if error is not None:
             raise error
         if same:
-            first = planes[scene.sources[self.spp].index(scene.target)]
+            first = planes[renderings.index(scene.target)]
             planes[self.S] = {name: first[name] for name in self.target_channels}
         return planes
 

@@ -772,6 +772,49 @@ typedef struct { int n_passes; int n_planes; const int* plane_hw; dd_tile_pass p
 int dd_sample_tiles(const dd_tile_sampler_desc* desc, const dd_tile_record* records, int B, int T, int use_flip, int use_rotate,
                     int use_permute, int use_normal_rotation, dd_stream stream);
 
+/* ---- data-set statistics of frames that stay in device memory (csrc/dd_frame_statistics.hip).  Replaces the two sweeps over a tile set on
+ * disk by which the reference makes <mode>_statistics.json (TFRecordsStatistics.py:109-140 and :162-193, per tile
+ * _first_statistics_iteration :236-285 and _second_statistics_iteration :287-316; the tiles are the grid of TFRecordsCreator.py:125-133):
+ * ONE launch reads every sample of every (window, pass) once and writes a row of DD_STAT_FIELDS doubles per (window, pass),
+ *     out[(window * n_passes + pass) * DD_STAT_FIELDS + field]
+ * from which the host joins the file (deepdenoiser_amd/statistics.py).  With x the T x T x C window of the pass, l = sign(x) log1p(|x|)
+ * (Utilities.signed_log1p), the pivot K = the window's first sample x[0, 0, 0] and Kl = signed_log1p(K), the fields are
+ *     DD_STAT_PRESENT                1.0, or 0.0: the plane does not hold the pass (a NULL plane pointer) or is smaller than a window;
+ *                                    every other field of such a row is 0
+ *     DD_STAT_MIN, _MAX              min x, max x                      DD_STAT_MIN_LOG1P, _MAX_LOG1P     min l, max l
+ *                                    (min l and max l are signed_log1p of min x and max x -- the function is monotone -- rounded to the
+ *                                    nearest double; the log1p inside the sums is the math library's, within an ulp)
+ *     DD_STAT_PIVOT, _PIVOT_LOG1P    K, Kl
+ *     DD_STAT_SUM, _SUM_SQ           sum (x - K), sum (x - K)^2        DD_STAT_SUM_LOG1P, _SUM_SQ_LOG1P  sum (l - Kl), sum (l - Kl)^2
+ *                                    over all T * T * C samples
+ *     DD_STAT_COUNT                  the number of pixels with sum_c |x_c| != 0 (Conv2dUtilities.non_zero_mask; is_alpha: x - 1 in place
+ *                                    of x, TFRecordsStatistics.py:262-264 and :277-280)
+ *     DD_STAT_MASK_SUM               sum over pixels of m = sign(sum_c |mask_c|), the mask pass read at the same window of mask_plane (:246-249)
+ *     DD_STAT_MASKED_SUM, ...        the four shifted sums with every term times m(pixel), over all three channels (:252, :258, :270, :309, :312)
+ * The sums are shifted because the global mean the variance is taken about (:289-290) is known only after every window has been seen: with
+ * d = mean - K,  sum (x - mean)^2 = sum (x - K)^2 - 2 d sum (x - K) + n d^2, and a plane is read once (a raw sum of squares would lose
+ * everything next to Blender's Depth of 1e10 where no surface is hit).  Without a mask (mask_planes NULL, a NULL mask plane pointer, or a mask
+ * plane smaller than a window) DD_STAT_MASK_SUM and the masked sums are 0.
+ *   plane, plane_hw : as dd_sample_tiles: per pass a DEVICE array of n_planes base pointers (fp32 [h, w, C], contiguous, NULL where the pass
+ *             is not loaded), and the DEVICE table [n_planes][2] of (h, w).  mask_planes: the same array of the target COLOUR pass
+ *             (3 channels) the pass is masked by, or NULL.
+ *   window  : DEVICE table.  Windows cannot be checked on the host; the kernel clamps plane and mask_plane into 0 .. n_planes-1 and the
+ *             origin into [0, h-T] x [0, w-T] of the plane it reads (the mask plane's own size for the mask), so a bad window reads no byte
+ *             outside a plane.
+ * log1p and every sum are double.  The order of a sum is fixed (a thread's pixels in ascending order, a shift-down tree over the wave, the
+ * waves in order through LDS) and there are no atomics: two launches on the same input give the same bytes.
+ * desc is a HOST struct (copied by value).  Refused with a negative status and no launch: NULL pointers, n_passes outside
+ * 1 .. DD_STAT_MAX_PASSES, C outside {1, 3}, a mask pass on a pass with C != 3 (the reference stacks the mask three times, :252), T < 1 (or
+ * above 16384), n_windows < 1.  No host sync. */
+#define DD_STAT_MAX_PASSES 64
+enum { DD_STAT_PRESENT = 0, DD_STAT_MIN, DD_STAT_MAX, DD_STAT_MIN_LOG1P, DD_STAT_MAX_LOG1P, DD_STAT_PIVOT, DD_STAT_PIVOT_LOG1P,
+       DD_STAT_SUM, DD_STAT_SUM_SQ, DD_STAT_SUM_LOG1P, DD_STAT_SUM_SQ_LOG1P, DD_STAT_COUNT, DD_STAT_MASK_SUM,
+       DD_STAT_MASKED_SUM, DD_STAT_MASKED_SUM_SQ, DD_STAT_MASKED_SUM_LOG1P, DD_STAT_MASKED_SUM_SQ_LOG1P, DD_STAT_FIELDS };
+typedef struct { int plane; int mask_plane; int y0; int x0; } dd_stat_window;
+typedef struct { const float* const* planes; const float* const* mask_planes; int C; int is_alpha; } dd_stat_pass;
+typedef struct { int n_passes; int n_planes; const int* plane_hw; dd_stat_pass pass[DD_STAT_MAX_PASSES]; } dd_stat_desc;
+int dd_tile_statistics(const dd_stat_desc* desc, const dd_stat_window* windows, int n_windows, int T, double* out, dd_stream stream);
+
 /* 3x3/s2 transpose conv (Tiramisu.py:62-64) = 3x3 SAME conv of the zero-stuffed input with the flipped kernel:
  * y[B,2H,2W,C] = 0 except y[2i+1,2j+1] = x[i,j]; and its adjoint dx[i,j] (+)= dy[2i+1,2j+1] * (mask>0). */
 int dd_zero_stuff(const void* x, int ldx, void* y, int ldy, int C, int B, int H, int W, int dtype, dd_stream stream);
