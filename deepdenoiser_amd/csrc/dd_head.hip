@@ -285,7 +285,7 @@ __global__ __launch_bounds__(256) void head_fwd_kernel(const HeadP a) {
   SegWalk sw = seg_start(wave * per_wave, per_wave, nsegs, nseg_x, a.H);
   for (; sw.left > 0; seg_next(sw, nseg_x, a.H)) {
     const PixelAddr pa = seg_pixel(sw, li, a);
-    const int pix = (pa.b * a.H + pa.y) * a.W + pa.x;                    // (npix < 2^31: checked by the host)
+    const int pix = (pa.b * a.H + pa.y) * a.W + pa.x;                    // (npix < 2^31: checked by the host, head_common)
     uint4 xf[NCH];
     load_x<T, NCH>(xf, a, pix, q);
     const float* img = a.src + (long)pa.b * a.H * a.W * a.ldsrc;
@@ -755,13 +755,16 @@ int head_common(const dd_head_args* a, bool backward, dd_stream stream) {
   DD_REQUIRE(a->C > 0 && a->C % 8 == 0 && a->ldx >= a->C && a->ldx % 8 == 0 && ((uintptr_t)a->x % 16) == 0, "dd_kpcn_head: C=%d ldx=%d must be multiples of 8, x 16-byte aligned", a->C, a->ldx);
   DD_REQUIRE(a->N > 0 && a->H > 0 && a->W > 0 && a->ldsrc >= 3, "dd_kpcn_head: bad shape");
   DD_REQUIRE(a->H >= (a->ksize - 1) / 2 && a->W >= (a->ksize - 1) / 2, "dd_kpcn_head: image smaller than the symmetric pad");
+  // the kernels index pixels with an int and the taps of one image with a 32-bit element offset (load_taps)
+  DD_REQUIRE((long)a->N * a->H * a->W < (1L << 31) && (long)a->H * a->W * a->ldsrc < (1L << 32), "dd_kpcn_head: N*H*W must stay below 2^31 and H*W*ldsrc below 2^32");
   HeadP p;
   p.x = a->x; p.src = a->src; p.wa = a->wa; p.ba = a->ba; p.wb = a->wb; p.bb = a->bb; p.out = a->out;
   p.dout = a->dout; p.dx = a->dx; p.dwa = a->dwa; p.dba = a->dba; p.dwb = a->dwb; p.dbb = a->dbb;
   p.ldx = a->ldx; p.C = a->C; p.ldsrc = a->ldsrc; p.ldo = a->ld_out; p.lddo = a->ld_dout; p.lddx = a->ld_dx; p.accumulate = a->accumulate_dx;
   p.N = a->N; p.H = a->H; p.W = a->W; p.npix = (long)a->N * a->H * a->W;
   if (!backward) DD_REQUIRE(a->out && a->ld_out >= 3, "dd_kpcn_head_fwd: null output");
-  else DD_REQUIRE(a->dout && a->ld_dout >= 3 && a->dx && a->ld_dx >= a->C && a->ld_dx % 4 == 0 && a->dwa && a->dba && a->dwb && a->dbb, "dd_kpcn_head_bwd: null gradient pointer");
+  else DD_REQUIRE(a->dout && a->ld_dout >= 3 && a->dx && a->ld_dx >= a->C && a->ld_dx % 4 == 0 && ((uintptr_t)a->dx % 8) == 0 && a->dwa && a->dba && a->dwb && a->dbb,
+                  "dd_kpcn_head_bwd: null gradient pointer, or dx not 8-byte aligned with ld_dx a multiple of 4");
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   return a->dtype == DD_BF16 ? dispatch_ks<bf16_t>(p, a->ksize, backward, s) : dispatch_ks<f16_t>(p, a->ksize, backward, s);
 }
@@ -796,7 +799,9 @@ extern "C" int dd_kpcn_head_bwd_multi(const dd_head_args* a, int n, dd_stream st
                "dd_kpcn_head_bwd_multi: one storage type (bf16 / f16) and one kernel size (3, 5) per launch");
     DD_REQUIRE(b->C > 0 && b->C <= 128 && b->C % 8 == 0 && b->ldx >= b->C && b->ldx % 8 == 0 && ((uintptr_t)b->x % 16) == 0, "dd_kpcn_head_bwd_multi: C=%d ldx=%d (problem %d)", b->C, b->ldx, i);
     DD_REQUIRE(b->N > 0 && b->H > 0 && b->W > 0 && b->ldsrc >= 3 && b->H >= (b->ksize - 1) / 2 && b->W >= (b->ksize - 1) / 2, "dd_kpcn_head_bwd_multi: bad shape (problem %d)", i);
-    DD_REQUIRE(b->dout && b->ld_dout >= 3 && b->dx && b->ld_dx >= b->C && b->ld_dx % 4 == 0 && b->dwa && b->dba && b->dwb && b->dbb, "dd_kpcn_head_bwd_multi: null gradient pointer (problem %d)", i);
+    DD_REQUIRE((long)b->N * b->H * b->W < (1L << 31) && (long)b->H * b->W * b->ldsrc < (1L << 32), "dd_kpcn_head_bwd_multi: N*H*W must stay below 2^31 and H*W*ldsrc below 2^32 (problem %d)", i);
+    DD_REQUIRE(b->dout && b->ld_dout >= 3 && b->dx && b->ld_dx >= b->C && b->ld_dx % 4 == 0 && ((uintptr_t)b->dx % 8) == 0 && b->dwa && b->dba && b->dwb && b->dbb,
+               "dd_kpcn_head_bwd_multi: null gradient pointer, or dx not 8-byte aligned with ld_dx a multiple of 4 (problem %d)", i);
     HeadP& p = m.p[i];
     p.x = b->x; p.src = b->src; p.wa = b->wa; p.ba = b->ba; p.wb = b->wb; p.bb = b->bb; p.out = b->out;
     p.dout = b->dout; p.dx = b->dx; p.dwa = b->dwa; p.dba = b->dba; p.dwb = b->dwb; p.dbb = b->dbb;

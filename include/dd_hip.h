@@ -285,7 +285,8 @@ int dd_kpcn_hidden_bwd(const float* src, int ldsrc, const void* hid, int ldh, in
  * KernelPrediction.py:11-63) with K = ksize * ksize (one tuple member), and their TF-autodiff gradients.  bf16 / fp16 storage only.
  * Weights are the fp32 master variables in TensorFlow layout (wa [C][K], wb [K][K]).  The backward recomputes hid / logits from x, so
  * the forward stores nothing; dx (storage type) is masked by x > 0 (x is a ReLU output) and optionally accumulated into; the weight /
- * bias gradients are ADDED to their fp32 arena slots. */
+ * bias gradients are ADDED to their fp32 arena slots.  x 16-byte aligned with ldx % 8 == 0, dx 8-byte aligned with ld_dx % 4 == 0;
+ * H, W >= (ksize - 1) / 2; N * H * W < 2^31 and H * W * ldsrc < 2^32 (pixels and tap offsets are 32-bit in the kernels). */
 typedef struct {
   const void* x; int ldx; int C;           /* backbone output of this scale [N,H,W,ldx], C valid channels (C % 8 == 0, C <= 128) */
   const float* src; int ldsrc;             /* 3-channel source at this scale [N,H,W,ldsrc] fp32 */
