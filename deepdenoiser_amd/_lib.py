@@ -51,7 +51,7 @@ SYMBOLS = (
     "dd_histogram_values", "dd_loss_histograms_scratch_bytes", "dd_loss_histograms", "dd_loss_previews",
     "dd_nonfinite_scan", "dd_nonfinite_repair", "dd_frame_quality_scratch_bytes", "dd_frame_quality", "dd_stitch_blend",
     "dd_grad_norms", "dd_adam_step_clipped", "dd_adam_step_scaled_clipped", "dd_sample_tiles",
-    "dd_tile_statistics",
+    "dd_tile_statistics", "dd_importance_cells",
 )
 
 
@@ -242,6 +242,22 @@ class StatPass(C.Structure):           # dd_stat_pass: `planes` / `mask_planes` 
 
 class StatDesc(C.Structure):           # dd_stat_desc: a host struct, `plane_hw` is the device table [n_planes][2] of (h, w)
     _fields_ = [("n_passes", C.c_int), ("n_planes", C.c_int), ("plane_hw", C.c_void_p), ("pass_", StatPass * STAT_MAX_PASSES)]
+
+
+IMPORTANCE_MAX_PASSES = 16      # DD_IMPORTANCE_MAX_PASSES
+
+
+class ImportanceCell(C.Structure):     # dd_importance_cell: one G x G cell of dd_importance_cells, in device memory (16 bytes)
+    _fields_ = [("source_plane0", C.c_int), ("target_plane", C.c_int), ("y0", C.c_int), ("x0", C.c_int)]
+
+
+class ImportancePass(C.Structure):     # dd_importance_pass: `planes` is a device array of n_planes base pointers of a 3-channel colour pass
+    _fields_ = [("planes", C.c_void_p)]
+
+
+class ImportanceDesc(C.Structure):     # dd_importance_desc: a host struct, `plane_hw` is the device table [n_planes][2] of (h, w)
+    _fields_ = [("n_passes", C.c_int), ("n_planes", C.c_int), ("plane_hw", C.c_void_p), ("n_sources", C.c_int), ("epsilon", C.c_float),
+                ("pass_", ImportancePass * IMPORTANCE_MAX_PASSES)]
 
 
 class StitchEntry(C.Structure):
@@ -442,6 +458,7 @@ def load():
     lib.dd_kpcn_head_bwd_multi.argtypes = [C.POINTER(HeadArgs), i, vp]
     lib.dd_sample_tiles.argtypes = [C.POINTER(TileSamplerDesc), vp, i, i, i, i, i, i, vp]
     lib.dd_tile_statistics.argtypes = [C.POINTER(StatDesc), vp, i, i, vp, vp]
+    lib.dd_importance_cells.argtypes = [C.POINTER(ImportanceDesc), vp, i, i, vp, vp]
     _lib = lib
     return lib
 

@@ -7,9 +7,10 @@ TensorFlow 1.x and OpenCV).  Here the EXRs themselves are the data set:
                  (OpenEXRDirectories.py:18-29, OpenEXRDirectory.py:20, TFRecordsCreator.py:62-88); host only, reads EXR headers only
     FrameBank    the passes an architecture loads, of one samples-per-pixel count, decoded once and kept as fp32 planes on the device
                  (FrameBank.for_passes: a given set of passes, of one or several counts, without an architecture -- statistics.py)
-    TileSampler  a mini-batch = B windows of resident planes: `draw` picks them (random crops, or the reference's fixed grid of
-                 TFRecordsCreator.py:125-133), `sample` uploads the B records and makes ONE dd_sample_tiles launch that crops and augments
-                 every pass into the program's input and target buffers (csrc/dd_tile_sampler.hip)
+    TileSampler  a mini-batch = B windows of resident planes: `draw` picks them (random crops, the reference's fixed grid of
+                 TFRecordsCreator.py:125-133, or crops drawn where the noise is: frame_importance.py), `sample` uploads the B records and
+                 makes ONE dd_sample_tiles launch that crops and augments every pass into the program's input and target buffers
+                 (csrc/dd_tile_sampler.hip)
 
 A PLANE is one rendering of one scene.  Plane indices are shared by all passes: scene s of a bank with S sources per example owns planes
 s * (S + 1) + 0 .. S-1 (its source renderings, in path order) and s * (S + 1) + S (its target rendering).  A record is four int32
@@ -271,6 +272,13 @@ class TileRecords:
     def __init__(self, bank, B):
         self.bank, self.B, self.T = bank, int(B), bank.tile
         self._order, self._cursor = None, 0
+        self.importance = None
+
+    def set_importance(self, importance):
+        """Attach the frame_importance.ImportanceMap of this bank: `draw` then knows the crops 'importance'."""
+        if importance.tile != self.T or importance.sizes != [(s.height, s.width) for s in self.bank.scenes]:
+            raise ValueError("the importance map was made for other frames: tiles of %d, scenes %s" % (importance.tile, importance.sizes))
+        self.importance = importance
 
     def grid_records(self, index_tuples):
         """The reference's tile set (TFRecordsCreator.py:125-133 times Training.py:544-549) as records [n, 4] int32 (source plane, target
@@ -281,7 +289,7 @@ class TileRecords:
         return np.asarray(out, dtype=np.int32).reshape(-1, 4)
 
     def epoch_examples(self, index_tuples):
-        """Examples of an epoch, in either crop mode: the size of the grid set."""
+        """Examples of an epoch, in every crop mode: the size of the grid set."""
         return sum((s.height // self.T) * (s.width // self.T) for s in self.bank.scenes) * len(index_tuples)
 
     def reset(self):
@@ -291,9 +299,12 @@ class TileRecords:
         """The records [B, 4] of this rank's next mini-batch, or None when the epoch holds no further whole round of `world` mini-batches
         (the next call then starts an epoch).  `rng`: the random.Random all ranks share -- every rank draws the same world * B examples and
         takes examples rank * B .. (rank + 1) * B - 1 of them.  crops 'random': scene uniform, origin uniform in [0, h-T] x [0, w-T], source
-        index from a uniformly chosen index tuple; 'grid': the grid set, shuffled once per epoch and handed out in that order."""
-        if crops not in ("random", "grid"):
-            raise ValueError("crops: 'random' or 'grid', not %r" % (crops,))
+        index from a uniformly chosen index tuple; 'grid': the grid set, shuffled once per epoch and handed out in that order; 'importance':
+        as 'random', every example by ImportanceMap.draw of the attached map (set_importance)."""
+        if crops not in ("random", "grid", "importance"):
+            raise ValueError("crops: 'random', 'grid' or 'importance', not %r" % (crops,))
+        if crops == "importance" and self.importance is None:
+            raise ValueError("crops 'importance': no importance map is attached (TileRecords.set_importance)")
         bank, T, need = self.bank, self.T, self.B * world
         if self._order is None:
             self._cursor = 0
@@ -310,6 +321,11 @@ class TileRecords:
             return None
         if crops == "grid":
             drawn = self._order[self._cursor:self._cursor + need]
+        elif crops == "importance":
+            drawn = np.empty((need, 4), dtype=np.int32)
+            for k in range(need):
+                s, y0, x0, tup = self.importance.draw(rng, index_tuples)
+                drawn[k] = (bank.source_plane(s, tup[0]), bank.target_plane(s), y0, x0)
         else:
             drawn = np.empty((need, 4), dtype=np.int32)
             for k in range(need):

@@ -30,7 +30,10 @@ rendered EXRs the TFRecords-JSON names are decoded once and kept as fp32 planes 
 not read and no .tfrecords file is needed.  A mini-batch is then B records (plane, origin, augmentation draw) and ONE dd_sample_tiles launch
 that crops and augments every pass into the program's input and target buffers; TileStream, Uploader and DataAugmentation.apply are not
 used.  `--frames_crops random` cuts the tiles anywhere in a frame, `grid` on the fixed grid of the tile sets; an epoch has as many examples
-as the grid in either mode.  Validation runs over the grid of the JSON's validation mode, without augmentation."""
+as the grid in either mode.  `--frames_crops importance` draws the tiles where the noisy sources differ from the target: one
+dd_importance_cells launch scores the training frames when they are loaded, the draw stays on the host (frame_importance.py; the floor
+`--frames_importance_floor`, the cell side `--frames_importance_cell`, the density as pictures `--frames_importance_png`).  Validation runs
+over the grid of the JSON's validation mode, without augmentation."""
 import argparse
 import json
 import multiprocessing
@@ -52,8 +55,27 @@ from .tiling import source_index_tuples
 from .training import Trainer
 
 
+IMPORTANCE_FLAGS = ("frames_importance_floor", "frames_importance_cell", "frames_importance_png")
+
+
+class _Parser(argparse.ArgumentParser):
+    """The sub-options of `--frames_crops importance` are refused without it (by name); the floor's default is filled in afterwards, so that
+    a given value can be told from the default."""
+
+    def parse_args(self, args=None, namespace=None):
+        ns = super().parse_args(args, namespace)
+        if ns.frames_crops != "importance":
+            for name in IMPORTANCE_FLAGS:
+                if getattr(ns, name) is not None:
+                    self.error("--%s needs --frames_crops importance" % name)
+        if ns.frames_importance_floor is None:
+            from .frame_importance import DEFAULT_FLOOR
+            ns.frames_importance_floor = DEFAULT_FLOOR
+        return ns
+
+
 def parser():
-    p = argparse.ArgumentParser(description="Training for the DeepDenoiser (MI355X-native hot path).")
+    p = _Parser(description="Training for the DeepDenoiser (MI355X-native hot path).")
     p.add_argument("json_filename", help="The json specifying all the relevant details.")
     p.add_argument("--validate", action="store_true", help="Perform a validation step.")
     p.add_argument("--threads", type=int, default=multiprocessing.cpu_count() + 1, help="Number of threads to use (host-side decoding)")
@@ -90,9 +112,19 @@ def parser():
                         "TFRecordsExample.json) that names the scene directories.  Overrides the optional \"frames\" of Training.json; "
                         "base_tfrecords_directory is then not read.")
     p.add_argument("--frames_spp", type=int, default=None, help="Samples per pixel of the source renderings (default: the first of source.samples_per_pixel).")
-    p.add_argument("--frames_crops", default="random", choices=["random", "grid"],
-                   help="Where the tiles of a mini-batch are cut: anywhere in a frame, or on the fixed grid of the .tfrecords tile sets "
-                        "(shuffled per epoch).  An epoch has as many examples as the grid in either mode.")
+    p.add_argument("--frames_crops", default="random", choices=["random", "grid", "importance"],
+                   help="Where the tiles of a mini-batch are cut: anywhere in a frame, on the fixed grid of the .tfrecords tile sets "
+                        "(shuffled per epoch), or anywhere with a probability that grows with the SMAPE between the noisy sources and the "
+                        "target inside the tile (scored on the device when the frames are loaded; this changes the training distribution on "
+                        "purpose, no loss re-weighting is applied).  An epoch has as many examples as the grid in every mode.")
+    p.add_argument("--frames_importance_floor", type=float, default=None, metavar="F",
+                   help="With --frames_crops importance: the share of the draws that ignores the scores (0 .. 1), so that easy regions do not "
+                        "vanish.  Default 0.25: a choice, not a measured optimum.")
+    p.add_argument("--frames_importance_cell", type=int, default=None, metavar="G",
+                   help="With --frames_crops importance: the side of the cells the frames are scored in (1 .. 64, a divisor of the tile; "
+                        "default: the largest of 16, 8, 4, 2, 1 that divides it).")
+    p.add_argument("--frames_importance_png", default=None, metavar="DIR",
+                   help="With --frames_crops importance: rank 0 writes the density as <scene directory name>_importance.png per training scene into DIR.")
     p.add_argument("--frame_memory_gb", type=float, default=None,
                    help="The most device memory the frames may take (default: 80 %% of what is free when they are loaded).")
     p.add_argument("--seed", type=int, default=0, help="seed of the file / example shuffles and of the source index tuples (shared by all ranks)")
@@ -452,6 +484,17 @@ def main(args):
             return TileSampler(trainer.program, bank, usage)
         if not args.validate:
             sampler = resident("training", frame_set)
+            if args.frames_crops == "importance":      # scored once, on every rank (each holds the whole bank: the same table everywhere)
+                from .frame_importance import ImportanceMap
+                importance = ImportanceMap(sampler.bank, cell=args.frames_importance_cell, floor=args.frames_importance_floor)
+                sampler.set_importance(importance)
+                quiet(importance.describe())
+                if args.frames_importance_png is not None and rank == 0:
+                    os.makedirs(args.frames_importance_png, exist_ok=True)
+                    for s, scene in enumerate(sampler.bank.scenes):
+                        name = os.path.basename(os.path.normpath(scene.directory)) + "_importance.png"
+                        with open(os.path.join(args.frames_importance_png, name), "wb") as f:
+                            f.write(summaries.encode_png(importance.picture(s)))
         with open(frames_json, encoding="utf-8") as f:
             validate = validate and "validation" in json.load(f)["modes"]
         if validate or args.validate:

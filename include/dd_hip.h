@@ -816,6 +816,33 @@ typedef struct { const float* const* planes; const float* const* mask_planes; in
 typedef struct { int n_passes; int n_planes; const int* plane_hw; dd_stat_pass pass[DD_STAT_MAX_PASSES]; } dd_stat_desc;
 int dd_tile_statistics(const dd_stat_desc* desc, const dd_stat_window* windows, int n_windows, int T, double* out, dd_stream stream);
 
+/* ---- importance scores of frames that stay in device memory (csrc/dd_frame_importance.hip): how much the noisy source renderings differ
+ * from the target rendering, per G x G cell, in the measure of the loss itself -- the SMAPE of LossDifference.py:30-34 with its default
+ * epsilon.  The reference fixes its training tiles on disk once and for all (TFRecordsCreator.py:125-133: the grid of non-overlapping tiles);
+ * with resident frames a training window can be drawn where the noise is (deepdenoiser_amd/frame_importance.py makes the density from these
+ * cells, `train.py --frames_crops importance`).  ONE launch reads every sample of the colour passes once and writes one double per cell:
+ * with t the cell's target plane and s_k the source planes source_plane0 + k, k < n_sources, over the G x G x 3 samples of every pass p,
+ *     out[n] = sum_p sum_k sum_pixels sum_c  |s_k - t| / ((|s_k| + |t|) + epsilon)
+ * A term is evaluated in fp32 in exactly that order with a division rounded to nearest (there is no product: nothing contracts into an FMA);
+ * the terms -- none negative, so nothing cancels -- are added in double.  A (pass, source) pair whose source or target plane pointer is NULL
+ * adds nothing; a cell one of whose planes is smaller than G x G gets out[n] = 0.
+ *   plane, plane_hw : as dd_sample_tiles: per pass a DEVICE array of n_planes base pointers (fp32 [h, w, 3], contiguous, NULL where the pass is
+ *             not loaded), and the DEVICE table [n_planes][2] of (h, w).  Every pass is a 3-channel colour pass.
+ *   cell    : DEVICE table.  Cells cannot be checked on the host; the kernel clamps target_plane into 0 .. n_planes-1, source_plane0 so that
+ *             source_plane0 + n_sources - 1 stays in that range, and the origin into [0, h-G] x [0, w-G] of the plane it reads, as
+ *             dd_tile_statistics does, so a bad cell reads no byte outside a plane.
+ * The order of a sum is fixed (one wave per cell; a lane's pixels in ascending row-major order, per pixel the passes in order, per pass the
+ * sources in order, channels 0 .. 2; the shift-down tree of dd_tile_statistics over the wave) and there are no atomics: two launches on the
+ * same input give the same bytes, so data-parallel ranks arrive at the same table.
+ * desc is a HOST struct (copied by value).  Refused with a negative status and no launch: NULL pointers, n_passes outside
+ * 1 .. DD_IMPORTANCE_MAX_PASSES, n_planes < 1, n_sources < 1, G outside 1 .. 64, n_cells < 1, an epsilon that is not positive and finite.
+ * No host sync. */
+#define DD_IMPORTANCE_MAX_PASSES 16
+typedef struct { int source_plane0; int target_plane; int y0; int x0; } dd_importance_cell;
+typedef struct { const float* const* planes; } dd_importance_pass;
+typedef struct { int n_passes; int n_planes; const int* plane_hw; int n_sources; float epsilon; dd_importance_pass pass[DD_IMPORTANCE_MAX_PASSES]; } dd_importance_desc;
+int dd_importance_cells(const dd_importance_desc* desc, const dd_importance_cell* cells, int n_cells, int G, double* out, dd_stream stream);
+
 /* 3x3/s2 transpose conv (Tiramisu.py:62-64) = 3x3 SAME conv of the zero-stuffed input with the flipped kernel:
  * y[B,2H,2W,C] = 0 except y[2i+1,2j+1] = x[i,j]; and its adjoint dx[i,j] (+)= dy[2i+1,2j+1] * (mask>0). */
 int dd_zero_stuff(const void* x, int ldx, void* y, int ldy, int C, int B, int H, int W, int dtype, dd_stream stream);
