@@ -51,7 +51,7 @@ SYMBOLS = (
     "dd_histogram_values", "dd_loss_histograms_scratch_bytes", "dd_loss_histograms", "dd_loss_previews",
     "dd_nonfinite_scan", "dd_nonfinite_repair", "dd_frame_quality_scratch_bytes", "dd_frame_quality", "dd_stitch_blend",
     "dd_grad_norms", "dd_adam_step_clipped", "dd_adam_step_scaled_clipped", "dd_sample_tiles",
-    "dd_tile_statistics", "dd_importance_cells",
+    "dd_tile_statistics", "dd_importance_cells", "dd_importance_update",
 )
 
 
@@ -260,6 +260,15 @@ class ImportanceDesc(C.Structure):     # dd_importance_desc: a host struct, `pla
                 ("pass_", ImportancePass * IMPORTANCE_MAX_PASSES)]
 
 
+class ImportanceUpdatePass(C.Structure):   # dd_importance_update_pass: a 3-channel colour pass, pred fp32 [B,T,T,pred_ld], target fp32 [B,T,T,target_ld]
+    _fields_ = [("pred", C.c_void_p), ("target", C.c_void_p), ("pred_ld", C.c_int), ("target_ld", C.c_int)]
+
+
+class ImportanceUpdateDesc(C.Structure):   # dd_importance_update_desc: a host struct, `plane_hw` and `cell_base` are device tables over the planes
+    _fields_ = [("n_passes", C.c_int), ("n_planes", C.c_int), ("plane_hw", C.c_void_p), ("cell_base", C.c_void_p), ("epsilon", C.c_float),
+                ("pass_", ImportanceUpdatePass * IMPORTANCE_MAX_PASSES)]
+
+
 class StitchEntry(C.Structure):
     _fields_ = [("tile", C.c_int), ("crop_y0", C.c_int), ("crop_y1", C.c_int), ("crop_x0", C.c_int),
                 ("crop_x1", C.c_int), ("dst_img", C.c_int), ("dst_y", C.c_int), ("dst_x", C.c_int)]
@@ -459,6 +468,7 @@ def load():
     lib.dd_sample_tiles.argtypes = [C.POINTER(TileSamplerDesc), vp, i, i, i, i, i, i, vp]
     lib.dd_tile_statistics.argtypes = [C.POINTER(StatDesc), vp, i, i, vp, vp]
     lib.dd_importance_cells.argtypes = [C.POINTER(ImportanceDesc), vp, i, i, vp, vp]
+    lib.dd_importance_update.argtypes = [C.POINTER(ImportanceUpdateDesc), vp, i, i, i, i, i, vp, vp, vp]
     _lib = lib
     return lib
 

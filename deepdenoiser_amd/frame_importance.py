@@ -22,14 +22,30 @@ The draw of one example, from the random.Random all ranks share (the ORDER of th
     tup = index_tuples[rng.randrange(len(index_tuples))]
 
 The scores are computed on the device because the planes live there; the draw stays on the host, like the two other crop modes.  The measure
-is noise only: no structure term (target gradients, normals), no refresh from the running model's loss, and no loss re-weighting -- this is a
-deliberate change of the training distribution, as in KPCN."""
+is noise only: no structure term (target gradients, normals) and no loss re-weighting -- this is a deliberate change of the training
+distribution, as in KPCN.
+
+Refreshed from the running model (`--frames_importance_refresh N`, off by default): after a few epochs the windows worth drawing are the
+ones the model still gets wrong.  The model's error of a cell is the mean SMAPE(prediction, target) with the same formula and epsilon as the
+noise score, the mean SMAPE(source, target) -- a network that returns its input scores exactly the noise map -- so the refreshed map needs
+no new unit:
+
+    score     ONE dd_importance_update launch (csrc/dd_importance_update.hip) inside every training step, between the forward and the backward
+              (Program.step_tail_ops: the backward may reuse prediction buffers), adds per cell that lies wholly inside an example's window
+              llrint(mean 2^32) and 1 to two flat integer tables on the device (ImportanceScorer)
+    fold      every N steps the tables are read, added over the ranks (an integer sum: exact) and zeroed; a visited cell moves towards the mean
+              m of its visits, cells = (1 - rate) cells + rate m, every other cell keeps its bytes, and weights, total and cdf are rebuilt
+              (ImportanceMap.fold).  The draw contract above is untouched.
+
+Visited cells fall as the model learns, unvisited ones keep their noise score and grow relatively heavier until they are visited; the floor
+keeps its role.  The refreshed map is not saved with a checkpoint: a resumed run starts from the noise map again."""
 import ctypes as C
 
 import numpy as np
 
 EPSILON = 1e-2            # LossDifference.difference's default epsilon
 DEFAULT_FLOOR = 0.25      # a choice, not a measured optimum
+DEFAULT_RATE = 0.5        # of a refresh (ImportanceMap.fold): a choice as well
 
 # dd_importance_cell as a numpy record (16 bytes)
 CELL_DTYPE = np.dtype([("source_plane0", "<i4"), ("target_plane", "<i4"), ("y0", "<i4"), ("x0", "<i4")])
@@ -132,6 +148,33 @@ class ImportanceMap:
         self.total = float(sum(W.sum() for W in self.weights))
         self.cdf = np.cumsum(np.concatenate([p.reshape(-1) for p in self.probabilities()]), dtype=np.float64)
 
+    def fold(self, sums, counts, rate):
+        """Move the visited cells towards the model's error there (ImportanceScorer.collect): for every cell with counts > 0,
+        m = sums / 2^32 / counts and cells = (1 - rate) cells + rate m in float64; every other cell keeps its bytes.  sums, counts: flat integer
+        tables over all cells, scenes in order, row-major (cell_table's order).  Weights, total, cdf and n_lattice are rebuilt by _finish; the
+        draw contract is untouched.  Returns the number of cells folded."""
+        from types import SimpleNamespace
+        rate = float(rate)
+        if not 0.0 < rate <= 1.0:                              # (a NaN fails both comparisons)
+            raise ValueError("importance crops: rate=%r (above 0, at most 1)" % (rate,))
+        sums, counts = np.asarray(sums).reshape(-1), np.asarray(counts).reshape(-1)
+        n = sum(c.size for c in self.cells)
+        if sums.shape != (n,) or counts.shape != (n,):
+            raise ValueError("importance crops: tables of %d sums and %d counts for %d cells" % (sums.size, counts.size, n))
+        cells, at, folded = [], 0, 0
+        for c in self.cells:
+            cnt = counts[at:at + c.size].reshape(c.shape)
+            visited = cnt > 0
+            new = c.copy()
+            m = sums[at:at + c.size].reshape(c.shape)[visited].astype(np.float64) / 4294967296.0 / cnt[visited].astype(np.float64)
+            new[visited] = (1.0 - rate) * c[visited] + rate * m
+            cells.append(new)
+            folded += int(visited.sum())
+            at += c.size
+        like = SimpleNamespace(tile=self.tile, scenes=[SimpleNamespace(height=h, width=w) for h, w in self.sizes])
+        self._finish(like, cells, self.cell, self.floor, self.passes)
+        return folded
+
     def probabilities(self):
         """Per scene the float64 array of the lattice windows' probabilities; they sum to 1 over all scenes."""
         n = len(self.weights)
@@ -171,3 +214,84 @@ class ImportanceMap:
         if top == 0.0:
             return np.zeros(self.weights[s].shape, dtype=np.uint8)
         return np.rint(255.0 * self.weights[s] / top).astype(np.uint8)
+
+
+def cell_bases(bank, G):
+    """(cell_base, n_cells) of a bank: int32 per plane, for a target plane the index of its scene's first cell in cell_table's order, -1 for
+    every other plane."""
+    base, at = np.full(bank.n_planes, -1, dtype=np.int32), 0
+    for s, scene in enumerate(bank.scenes):
+        base[bank.target_plane(s)] = at
+        at += (scene.height // G) * (scene.width // G)
+    return base, at
+
+
+def reduce_tables(sums, counts, dist, device=None, group=None):
+    """The tables of all ranks added: ONE all_reduce(SUM) of int64 over [sums | counts] -- integers, so the result is exact and the same
+    bytes on every rank.  device: where the collective's tensor lives (the GPU under RCCL, None: the host, gloo)."""
+    import torch
+    n = len(sums)
+    packed = torch.from_numpy(np.concatenate([np.asarray(sums, dtype=np.uint64).view(np.int64), np.asarray(counts).astype(np.int64)]))
+    if device is not None:
+        packed = packed.to(device)
+    dist.all_reduce(packed, op=dist.ReduceOp.SUM, group=group)
+    packed = packed.cpu().numpy()
+    return packed[:n].view(np.uint64).copy(), packed[n:].astype(np.uint32)
+
+
+class ImportanceScorer:
+    """Scores every training step's mini-batch by the model's error (module docstring): one dd_importance_update launch in
+    `program.step_tail_ops`, over the head features that are loaded, have 3 channels and are named in `importance.passes`, at scale 0.
+    acc_sum (uint64) / acc_count (uint32): the flat device tables over all cells (torch holds them as int64 / int32: the same bytes)."""
+
+    def __init__(self, program, sampler, importance):
+        import torch
+        from . import _lib as L
+        from .loss_desc import block_ptr
+        bank, B, T, G = sampler.bank, program.B, importance.tile, importance.cell
+        if program.H != T or program.W != T or sampler.importance is not importance:
+            raise ValueError("importance refresh: the map is not the one attached to this sampler, or the program was built for other tiles")
+        wanted = list(importance.passes or ())
+        index = {f.name: i for i, f in enumerate(program.head) if f.load_data and f.number_of_channels == 3}
+        self.passes = [name for name in wanted if name in index]      # (the map's order: with the source in place of the prediction, its sums)
+        if not self.passes:
+            raise ValueError("importance refresh: the network predicts none of the colour passes the map was scored on (%s)" % ", ".join(wanted))
+        self.program, self.sampler, self.importance, self.B, self.T, self.G = program, sampler, importance, B, T, G
+        P, targets = program.predictions[0], program.targets[0]
+        assert P.dtype == "f32" and targets.dtype == torch.float32
+        d = self.desc = L.ImportanceUpdateDesc()
+        d.n_passes, d.n_planes, d.plane_hw, d.epsilon = len(self.passes), bank.n_planes, bank.plane_hw.data_ptr(), EPSILON
+        for en, name in zip(d.pass_, self.passes):
+            i = index[name]
+            en.pred, en.pred_ld = block_ptr(P, i * B), P.ld
+            en.target, en.target_ld = targets.data_ptr() + i * B * T * T * int(targets.shape[-1]) * 4, int(targets.shape[-1])
+        base, self.n_cells = cell_bases(bank, G)
+        self.device = bank.device
+        self.cell_base = torch.from_numpy(base).to(bank.device)
+        d.cell_base = self.cell_base.data_ptr()
+        self.acc_sum = torch.zeros(self.n_cells, dtype=torch.int64, device=bank.device)
+        self.acc_count = torch.zeros(self.n_cells, dtype=torch.int32, device=bank.device)
+        # training always samples with draws, so the switches dd_sample_tiles was given are constants of the sampler's usage
+        flip, rotate = int(bool(sampler.usage.use_flip_left_right)), int(bool(sampler.usage.use_rotate_90))
+        lib, records = L.load(), sampler._records_dev
+
+        def run(stream, d=d, keep=(P.buf, targets, records, self.cell_base, self.acc_sum, self.acc_count)):
+            L.check(lib.dd_importance_update(C.byref(d), records.data_ptr(), B, T, G, flip, rotate, self.acc_sum.data_ptr(),
+                                             self.acc_count.data_ptr(), stream))
+        run.info = None
+        self.op = run
+        program.add_step_tail_op(run, "importance_update")
+
+    def tables(self):
+        """(sums uint64, counts uint32) as they stand on the device (waits for the stream)."""
+        return self.acc_sum.cpu().numpy().view(np.uint64), self.acc_count.cpu().numpy().view(np.uint32)
+
+    def collect(self, dist=None):
+        """(sums, counts) since the last call, added over the ranks of `dist` (torch.distributed, every rank calls); the device tables are
+        zeroed.  Copying them to the host waits for the stream."""
+        sums, counts = self.tables()
+        self.acc_sum.zero_()
+        self.acc_count.zero_()
+        if dist is not None:
+            sums, counts = reduce_tables(sums, counts, dist, device=self.device)
+        return sums, counts

@@ -32,8 +32,11 @@ that crops and augments every pass into the program's input and target buffers; 
 used.  `--frames_crops random` cuts the tiles anywhere in a frame, `grid` on the fixed grid of the tile sets; an epoch has as many examples
 as the grid in either mode.  `--frames_crops importance` draws the tiles where the noisy sources differ from the target: one
 dd_importance_cells launch scores the training frames when they are loaded, the draw stays on the host (frame_importance.py; the floor
-`--frames_importance_floor`, the cell side `--frames_importance_cell`, the density as pictures `--frames_importance_png`).  Validation runs
-over the grid of the JSON's validation mode, without augmentation."""
+`--frames_importance_floor`, the cell side `--frames_importance_cell`, the density as pictures `--frames_importance_png`).  With
+`--frames_importance_refresh N` the scores follow the model: one dd_importance_update launch inside every step scores the cells the
+mini-batch covers by the SMAPE between prediction and target, and every N steps the visited cells of the map move towards it by
+`--frames_importance_rate` (all ranks add their integer tables, so all hold the same map).  Validation runs over the grid of the JSON's
+validation mode, without augmentation."""
 import argparse
 import json
 import multiprocessing
@@ -55,12 +58,13 @@ from .tiling import source_index_tuples
 from .training import Trainer
 
 
-IMPORTANCE_FLAGS = ("frames_importance_floor", "frames_importance_cell", "frames_importance_png")
+IMPORTANCE_FLAGS = ("frames_importance_floor", "frames_importance_cell", "frames_importance_png", "frames_importance_refresh")
 
 
 class _Parser(argparse.ArgumentParser):
-    """The sub-options of `--frames_crops importance` are refused without it (by name); the floor's default is filled in afterwards, so that
-    a given value can be told from the default."""
+    """The sub-options of `--frames_crops importance` are refused without it (by name), `--frames_importance_rate` without
+    `--frames_importance_refresh`; the defaults of the floor and the rate are filled in afterwards, so that a given value can be told from
+    the default."""
 
     def parse_args(self, args=None, namespace=None):
         ns = super().parse_args(args, namespace)
@@ -68,9 +72,18 @@ class _Parser(argparse.ArgumentParser):
             for name in IMPORTANCE_FLAGS:
                 if getattr(ns, name) is not None:
                     self.error("--%s needs --frames_crops importance" % name)
+        if ns.frames_importance_refresh is None and ns.frames_importance_rate is not None:
+            self.error("--frames_importance_rate needs --frames_importance_refresh")
+        if ns.frames_importance_refresh is not None and ns.frames_importance_refresh < 1:
+            self.error("--frames_importance_refresh: %d (at least 1 step)" % ns.frames_importance_refresh)
         if ns.frames_importance_floor is None:
             from .frame_importance import DEFAULT_FLOOR
             ns.frames_importance_floor = DEFAULT_FLOOR
+        if ns.frames_importance_rate is None:
+            from .frame_importance import DEFAULT_RATE
+            ns.frames_importance_rate = DEFAULT_RATE
+        elif not 0.0 < ns.frames_importance_rate <= 1.0:
+            self.error("--frames_importance_rate: %r (above 0, at most 1)" % ns.frames_importance_rate)
         return ns
 
 
@@ -125,6 +138,13 @@ def parser():
                         "default: the largest of 16, 8, 4, 2, 1 that divides it).")
     p.add_argument("--frames_importance_png", default=None, metavar="DIR",
                    help="With --frames_crops importance: rank 0 writes the density as <scene directory name>_importance.png per training scene into DIR.")
+    p.add_argument("--frames_importance_refresh", type=int, default=None, metavar="N",
+                   help="With --frames_crops importance: every N steps (at least 1) move the scores of the cells the mini-batches covered "
+                        "towards the error the model made there (the SMAPE between prediction and target, scored by one launch inside every "
+                        "step), so that the draws follow what the model still gets wrong.  Off by default; not saved with a checkpoint.")
+    p.add_argument("--frames_importance_rate", type=float, default=None, metavar="A",
+                   help="With --frames_importance_refresh: how far a visited cell moves towards the model's error at a refresh (above 0, at "
+                        "most 1; 1 replaces the score).  Default 0.5: a choice, not a measured optimum.")
     p.add_argument("--frame_memory_gb", type=float, default=None,
                    help="The most device memory the frames may take (default: 80 %% of what is free when they are loaded).")
     p.add_argument("--seed", type=int, default=0, help="seed of the file / example shuffles and of the source index tuples (shared by all ranks)")
@@ -471,7 +491,7 @@ def main(args):
         print("restored %s (global_step %d)" % (latest, step))
     validate = "validation" in tj["modes"]
     usage = DataAugmentationUsage.from_training_json(tj)
-    sampler = validation_sampler = None
+    sampler = validation_sampler = scorer = None
     if frame_set is not None:
         quiet = print if rank == 0 else (lambda *a: None)
         limit = None if args.frame_memory_gb is None else int(args.frame_memory_gb * 2 ** 30)
@@ -489,12 +509,19 @@ def main(args):
                 importance = ImportanceMap(sampler.bank, cell=args.frames_importance_cell, floor=args.frames_importance_floor)
                 sampler.set_importance(importance)
                 quiet(importance.describe())
-                if args.frames_importance_png is not None and rank == 0:
+
+                def write_importance_pngs():
+                    if args.frames_importance_png is None or rank != 0:
+                        return
                     os.makedirs(args.frames_importance_png, exist_ok=True)
                     for s, scene in enumerate(sampler.bank.scenes):
                         name = os.path.basename(os.path.normpath(scene.directory)) + "_importance.png"
                         with open(os.path.join(args.frames_importance_png, name), "wb") as f:
                             f.write(summaries.encode_png(importance.picture(s)))
+                write_importance_pngs()
+                if args.frames_importance_refresh is not None:      # one more launch inside the step, before the trainer builds its segments
+                    from .frame_importance import ImportanceScorer
+                    scorer = ImportanceScorer(trainer.program, sampler, importance)
         with open(frames_json, encoding="utf-8") as f:
             validate = validate and "validation" in json.load(f)["modes"]
         if validate or args.validate:
@@ -577,6 +604,22 @@ def main(args):
         dist.all_reduce(sums)
         return list(zip(names, prog.metric_values(sums.cpu().numpy(), count=world * B)))
 
+    def refresh_importance():
+        """Every rank: the tables of all ranks' steps since the last refresh, folded into the map the next draws come from (every rank takes
+        the same number of steps, so the collective lines up, and every rank ends with the same bytes).  Rank 0 reports."""
+        sums, counts = scorer.collect(dist)
+        folded = importance.fold(sums, counts, args.frames_importance_rate)
+        if rank != 0:
+            return
+        visited = counts > 0
+        error = float((sums[visited].astype(np.float64) / 4294967296.0 / counts[visited]).mean()) if folded else 0.0
+        share = folded / max(len(counts), 1)
+        print("frames: importance refresh at step %d -- %d cells folded (%.1f %% of %d), mean model error %.4f, the heaviest tenth of the "
+              "windows holds %.1f %% of the weight" % (step, folded, 100.0 * share, len(counts), error, 100.0 * importance.heaviest_tenth_share()))
+        write_importance_pngs()
+        if writer is not None:
+            writer.add_scalars(step, [("frames_importance/folded_share", share), ("frames_importance/model_error", error)])
+
     gen = torch.Generator().manual_seed(1234 + rank)
     uploader = Uploader(arch.device) if sampler is None else None
     main_stream = torch.cuda.current_stream()
@@ -629,6 +672,8 @@ def main(args):
             scalars, histos = tracked_scalars(forwarded=show) if summary else (None, None)
             loss = trainer.step()
             step += 1
+            if scorer is not None and step % args.frames_importance_refresh == 0:
+                refresh_importance()
             if shown is not None:
                 writer.add_images(step, preview_summaries(trainer.program, shown, preview))
             if summary:

@@ -109,7 +109,10 @@ class Trainer:
         prog, ps = self.program, self.arch.params
         g = prog.g
         # label-only launches (scaled targets, mask counts) join segment 0 unless the mask counts need their all-reduce first
-        head = list(g.pack_ops) + ([] if self._reduce_masks else list(prog.label_ops)) + list(g.fwd_ops)
+        # step tail ops (Program.step_tail_ops: they read the predictions the backward may overwrite) go behind the forward; from here on the
+        # list is part of the segments, and of the hipGraph once it is captured
+        head = list(g.pack_ops) + ([] if self._reduce_masks else list(prog.label_ops)) + list(g.fwd_ops) + list(prog.step_tail_ops)
+        prog.step_tail_frozen, self._tail_ops = True, len(prog.step_tail_ops)
         bwd = list(g.bwd_ops)
         last_writer = {}
         for i, op in enumerate(bwd):
@@ -144,6 +147,9 @@ class Trainer:
         prog = self.program
         if self._segments is None:
             self._build_segments()
+        elif len(prog.step_tail_ops) != self._tail_ops:
+            raise RuntimeError("Program.step_tail_ops changed after the trainer had built its segments (%d launches then, %d now)"
+                               % (self._tail_ops, len(prog.step_tail_ops)))
         if self._reduce_masks:
             prog.run_label_ops()              # eager, outside the hipGraphs: contains a collective
         if self.use_graph and self._graphs is None and self._warm >= 2:

@@ -843,6 +843,39 @@ typedef struct { const float* const* planes; } dd_importance_pass;
 typedef struct { int n_passes; int n_planes; const int* plane_hw; int n_sources; float epsilon; dd_importance_pass pass[DD_IMPORTANCE_MAX_PASSES]; } dd_importance_desc;
 int dd_importance_cells(const dd_importance_desc* desc, const dd_importance_cell* cells, int n_cells, int G, double* out, dd_stream stream);
 
+/* ---- importance scores refreshed from the running model's error (csrc/dd_importance_update.hip).  dd_importance_cells measures noise only
+ * and its scores never change while the network trains; this launch scores the mini-batch that was just forwarded in the SAME measure -- the
+ * mean SMAPE(prediction, target) of a cell, so a network that returns its input scores exactly the noise map -- and the host moves the
+ * visited cells of the density towards it (deepdenoiser_amd/frame_importance.py: ImportanceScorer, ImportanceMap.fold;
+ * `train.py --frames_importance_refresh`).  It runs inside the step, between the forward and the first backward launch (the backward may
+ * reuse prediction buffers).
+ *   records : DEVICE, the table dd_sample_tiles has just cut the mini-batch from; use_flip / use_rotate: the switches it was given.
+ *   pass    : a 3-channel colour pass: pred fp32 [B, T, T, pred_ld], target fp32 [B, T, T, target_ld], both leading dimensions >= 3.
+ *   cell    : the G x G cells of a scene, h / G by w / G, row-major, scenes in order (the order of dd_importance_cells' table as
+ *             frame_importance.cell_table writes it).  cell_base is a DEVICE int[n_planes]: for a target plane the index of its scene's first
+ *             cell in the flat accumulators, -1 for every other plane.  plane_hw: as dd_sample_tiles.
+ * With (y0, x0) an example's origin in its target plane, the cells (cy, cx) that lie WHOLLY inside [y0, y0 + T) x [x0, x0 + T) are scored
+ * (per axis T / G of them when the origin is a multiple of G, T / G - 1 otherwise); a cell the window covers in part gets nothing.  The pixel
+ * (fy, fx) of the un-augmented window is read at the one tile pixel that shows it: the inverse of dd_sample_tiles' geometry for the record's
+ * rotate & 3 and flip under the two switches (the RGB permutation and the normal rotation do not matter: prediction and target carry the same
+ * permutation and a term is summed over the channels).  One wave per (example, cell slot); a lane owns the cell's pixels l, l + 64, ... in
+ * the FRAME's row-major order, per pixel the passes in order, channels 0 .. 2; a term is |p - t| / ((|p| + |t|) + epsilon) in fp32 in exactly
+ * that order with a division rounded to nearest, the terms are added in double and the lanes combined by dd_importance_cells' shift-down tree
+ * -- with the prediction replaced by the sampled source tile the sum is the one dd_importance_cells forms.  Then
+ *     mean = sum / (G G 3 n_passes);   finite:  acc_sum[cell] += llrint(mean 2^32),  acc_count[cell] += 1     (integer atomics)
+ * and a mean that is not finite (an fp16 overflow or a NaN in a prediction) adds nothing.  Integer sums do not depend on the order of the
+ * adds: two runs over the same predictions leave the same bytes, and data-parallel ranks can add their tables exactly.
+ * Records cannot be checked on the host; the kernel clamps the target plane index into 0 .. n_planes-1 and the origin into
+ * [0, h-T] x [0, w-T] as dd_sample_tiles does; a plane smaller than a tile, or one with cell_base < 0, adds nothing.
+ * desc is a HOST struct (copied by value).  Refused with a negative status and no launch: NULL pointers, n_passes outside
+ * 1 .. DD_IMPORTANCE_MAX_PASSES, pred_ld or target_ld below 3, G outside 1 .. 64 or not a divisor of T, T < 1, B < 1 (or above
+ * dd_sample_tiles' bounds), n_planes < 1, an epsilon that is not positive and finite.  No host sync. */
+typedef struct { const float* pred; const float* target; int pred_ld; int target_ld; } dd_importance_update_pass;
+typedef struct { int n_passes; int n_planes; const int* plane_hw; const int* cell_base; float epsilon;
+                 dd_importance_update_pass pass[DD_IMPORTANCE_MAX_PASSES]; } dd_importance_update_desc;
+int dd_importance_update(const dd_importance_update_desc* desc, const dd_tile_record* records, int B, int T, int G, int use_flip, int use_rotate,
+                         unsigned long long* acc_sum, unsigned int* acc_count, dd_stream stream);
+
 /* 3x3/s2 transpose conv (Tiramisu.py:62-64) = 3x3 SAME conv of the zero-stuffed input with the flipped kernel:
  * y[B,2H,2W,C] = 0 except y[2i+1,2j+1] = x[i,j]; and its adjoint dx[i,j] (+)= dy[2i+1,2j+1] * (mask>0). */
 int dd_zero_stuff(const void* x, int ldx, void* y, int ldy, int C, int B, int H, int W, int dtype, dd_stream stream);
