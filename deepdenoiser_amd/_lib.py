@@ -51,7 +51,7 @@ SYMBOLS = (
     "dd_histogram_values", "dd_loss_histograms_scratch_bytes", "dd_loss_histograms", "dd_loss_previews",
     "dd_nonfinite_scan", "dd_nonfinite_repair", "dd_frame_quality_scratch_bytes", "dd_frame_quality", "dd_stitch_blend",
     "dd_grad_norms", "dd_adam_step_clipped", "dd_adam_step_scaled_clipped", "dd_sample_tiles",
-    "dd_tile_statistics", "dd_importance_cells", "dd_importance_update",
+    "dd_tile_statistics", "dd_importance_cells", "dd_importance_update", "dd_exr_reconstruct",
 )
 
 
@@ -269,6 +269,18 @@ class ImportanceUpdateDesc(C.Structure):   # dd_importance_update_desc: a host s
                 ("pass_", ImportanceUpdatePass * IMPORTANCE_MAX_PASSES)]
 
 
+EXR_MAX_CHANNELS = 8            # DD_EXR_MAX_CHANNELS
+
+
+class ExrChunk(C.Structure):           # dd_exr_chunk: one scan-line chunk in the staged buffer of dd_exr_reconstruct (24 bytes)
+    _fields_ = [("offset", C.c_longlong), ("file", C.c_int), ("row0", C.c_int), ("rows", C.c_int), ("coded", C.c_int)]
+
+
+class ExrFile(C.Structure):            # dd_exr_file: the plane a file is decoded into and, per file channel, its pixel type and destination set
+    _fields_ = [("dst", C.c_void_p), ("H", C.c_int), ("W", C.c_int), ("C", C.c_int), ("n_channels", C.c_int),
+                ("type", C.c_int * EXR_MAX_CHANNELS), ("dst_mask", C.c_uint * EXR_MAX_CHANNELS)]
+
+
 class StitchEntry(C.Structure):
     _fields_ = [("tile", C.c_int), ("crop_y0", C.c_int), ("crop_y1", C.c_int), ("crop_x0", C.c_int),
                 ("crop_x1", C.c_int), ("dst_img", C.c_int), ("dst_y", C.c_int), ("dst_x", C.c_int)]
@@ -469,6 +481,7 @@ def load():
     lib.dd_tile_statistics.argtypes = [C.POINTER(StatDesc), vp, i, i, vp, vp]
     lib.dd_importance_cells.argtypes = [C.POINTER(ImportanceDesc), vp, i, i, vp, vp]
     lib.dd_importance_update.argtypes = [C.POINTER(ImportanceUpdateDesc), vp, i, i, i, i, i, vp, vp, vp]
+    lib.dd_exr_reconstruct.argtypes = [vp, vp, i, vp, vp, i, vp, l, vp, vp]
     _lib = lib
     return lib
 

@@ -134,9 +134,11 @@ class FrameBank:
 
     planes[name][p]: the tensor of pass `name` in plane p, or None (a pass that is only a source has no tensor in a target plane);
     pointers[name]: the same as a device int64 array (0 where None); plane_hw: device int32 [n_planes, 2]; hw: the same on the host.
-    A scene with a non-finite sample is skipped with one line through `log` (OpenEXRDirectory.py:72-76)."""
+    A scene with a non-finite sample is skipped with one line through `log` (OpenEXRDirectory.py:72-76).
+    decode: 'host' -- every file goes through openexr.read_image on `threads` threads and is uploaded; 'device' -- the host only inflates and
+    one dd_exr_reconstruct launch per scene rebuilds the planes on the device (openexr.DeviceDecoder): the same planes, bit for bit."""
 
-    def __init__(self, arch, frame_set, spp=None, device=None, memory_limit_bytes=None, threads=4, log=print):
+    def __init__(self, arch, frame_set, spp=None, device=None, memory_limit_bytes=None, threads=4, log=print, decode="host"):
         self.frame_set, self.tile, self.S = frame_set, frame_set.tile, frame_set.number_of_sources_per_example
         self.spp = int(frame_set.source_spps[0] if spp is None else spp)
         self.device = torch.device(arch.device if device is None else device)
@@ -148,13 +150,14 @@ class FrameBank:
             for name in need:
                 if name not in have:
                     raise ValueError("the architecture loads the %s pass '%s', which the frame set's %s features do not list" % (what, name, what))
-        self._load(frame_set.scenes, memory_limit_bytes, threads, log)
+        self._load(frame_set.scenes, memory_limit_bytes, threads, log, decode)
         if not self.scenes:
             raise ValueError("no usable scene is left (%d skipped)" % (len(frame_set.skipped) + len(self.skipped)))
         self._tables()
 
     @classmethod
-    def for_passes(cls, frame_set, source_channels, target_channels, spp, scenes=None, device="cuda", memory_limit_bytes=None, threads=4, log=print):
+    def for_passes(cls, frame_set, source_channels, target_channels, spp, scenes=None, device="cuda", memory_limit_bytes=None, threads=4, log=print,
+                   decode="host"):
         """A bank of the passes `source_channels` / `target_channels` ({pass name: channels}) without an Architecture: what the data-set
         statistics read (deepdenoiser_amd/statistics.py).  `spp`: one samples-per-pixel count or a list of them -- with a list a scene owns
         len(spp) * S source planes, those of the first count first, and `S` is that product, so source_plane / target_plane hold.  `scenes`:
@@ -167,11 +170,16 @@ class FrameBank:
                 raise ValueError("%d samples per pixel: the frame set lists %s" % (s, frame_set.source_spps))
         self.spp, self.S = self.spps[0], frame_set.number_of_sources_per_example * len(self.spps)
         self.source_channels, self.target_channels = dict(source_channels), dict(target_channels)
-        self._load(frame_set.scenes if scenes is None else scenes, memory_limit_bytes, threads, log)
+        self._load(frame_set.scenes if scenes is None else scenes, memory_limit_bytes, threads, log, decode)
         self._tables()
         return self
 
-    def _load(self, scenes, memory_limit_bytes, threads, log):
+    def _load(self, scenes, memory_limit_bytes, threads, log, decode="host"):
+        if decode not in ("host", "device"):
+            raise ValueError("decode: 'host' or 'device', not %r" % (decode,))
+        self.decode = decode
+        # (a decoder refuses a device that is no GPU with ValueError, before anything is read)
+        decoder = openexr.DeviceDecoder(self.device, threads=max(1, min(int(threads), 16))) if decode == "device" else None
         # ---- the bytes, before anything is allocated
         per_pixel = 4 * (self.S * sum(self.source_channels.values()) + sum(self.target_channels.values()))
         self.total_bytes = sum(s.height * s.width * per_pixel for s in scenes)
@@ -184,10 +192,11 @@ class FrameBank:
         self.threads = max(1, min(int(threads), 32))
         self.scenes, self.hw, self.skipped = [], [], []
         self.planes = {name: [] for name in set(self.source_channels) | set(self.target_channels)}
+        self.decoder = decoder                                # (None on the host path; its counters say what the load cost, tools/exr_decode_timing.py)
         with concurrent.futures.ThreadPoolExecutor(max_workers=self.threads) as pool:
             for scene in scenes:
                 try:
-                    loaded = self._load_scene(scene, pool)
+                    loaded = self._load_scene(scene, pool) if decoder is None else self._load_scene_device(scene, decoder)
                 except openexr.ExrError as e:
                     self.skipped.append((scene.directory, str(e)))
                     log("frames: %s skipped: %s" % (scene.directory, e))
@@ -197,6 +206,8 @@ class FrameBank:
                     self.hw.append((scene.height, scene.width))
                     for name in self.planes:
                         self.planes[name].append(plane.get(name))
+        if decoder is not None:
+            decoder.release()
 
     def _channels(self, arch):
         features = arch.feature_predictions + arch.auxiliary_features
@@ -254,6 +265,38 @@ class FrameBank:
                 error = error or e
         if error is not None:
             raise error
+        if same:
+            first = planes[renderings.index(scene.target)]
+            planes[self.S] = {name: first[name] for name in self.target_channels}
+        return planes
+
+    def _load_scene_device(self, scene, decoder):
+        """_load_scene with the files rebuilt on the device: one decode call for the scene, and the error of the first file that has one, in
+        the order _load_scene submits its jobs."""
+        renderings = [r for spp in self.spps for r in scene.sources[spp]]
+        jobs = [(p, r, name, ch) for p, r in enumerate(renderings) for name, ch in self.source_channels.items()]
+        same = scene.target in renderings
+        if not same:
+            jobs += [(self.S, scene.target, name, ch) for name, ch in self.target_channels.items()]
+        found = []
+        for p, rendering, name, ch in jobs:
+            try:
+                found.append(openexr.OpenEXRDirectory(rendering).file_of(name))
+            except openexr.ExrError as e:
+                found.append(e)
+        wanted = [k for k, path in enumerate(found) if not isinstance(path, openexr.ExrError)]
+        decoded = dict(zip(wanted, decoder.decode([(found[k], jobs[k][3]) for k in wanted], errors="return")))
+        planes = [{} for _ in range(self.S + 1)]
+        for k, (p, rendering, name, ch) in enumerate(jobs):
+            result = decoded.get(k, found[k])
+            if isinstance(result, openexr.ExrError):
+                raise result
+            image, nonfinite = result
+            if tuple(image.shape[:2]) != (scene.height, scene.width):
+                raise openexr.ExrError("%s is %dx%d, the scene is %dx%d" % (found[k], image.shape[1], image.shape[0], scene.width, scene.height))
+            if nonfinite:
+                raise openexr.ExrError("there is at least one value in %s which is not finite" % found[k])
+            planes[p][name] = image
         if same:
             first = planes[renderings.index(scene.target)]
             planes[self.S] = {name: first[name] for name in self.target_channels}

@@ -275,6 +275,254 @@ def write_image(path, image, compression=ZIP_COMPRESSION):
     return write_exr(path, {c: np.ascontiguousarray(image[..., i]) for i, c in enumerate("RGB")}, compression)
 
 
+# ---------------------------------------------------------------------------------------------------- decode on the device
+# The host keeps the header, the offset table and inflate (zlib releases the GIL); the predictor, the byte split, the row / channel split and
+# the conversion to fp32 are one dd_exr_reconstruct launch over the staged bytes of many files (csrc/dd_exr_decode.hip).
+_STAGE_ALIGN = 16                                               # a chunk's offset in the staged buffer; it owns the bytes up to the next multiple
+CHUNK_DTYPE = np.dtype([("offset", "<i8"), ("file", "<i4"), ("row0", "<i4"), ("rows", "<i4"), ("coded", "<i4")])      # dd_exr_chunk
+FILE_DTYPE = np.dtype([("dst", "<u8"), ("H", "<i4"), ("W", "<i4"), ("C", "<i4"), ("n_channels", "<i4"), ("type", "<i4", (8,)),
+                       ("dst_mask", "<u4", (8,))])                                                                       # dd_exr_file
+MAX_FILE_CHANNELS = 8                                           # DD_EXR_MAX_CHANNELS
+
+
+def _align(n):
+    return (n + _STAGE_ALIGN - 1) // _STAGE_ALIGN * _STAGE_ALIGN
+
+
+class FilePlan:
+    """What plan_file found in one file.  height, width, channels: the plane [height, width, channels] the file decodes to; types /
+    dst_masks: per file channel (header order) its pixel type and the set of plane channels it is written to (bit d = channel d);
+    chunks: CHUNK_DTYPE records with offsets relative to the file's staged bytes (`file` left 0); staged_bytes: how many there are;
+    pieces: per chunk (the chunk's bytes in the file, coded flag, bytes after inflate)."""
+
+    def __init__(self, path, height, width, channels, types, dst_masks, compression, chunks, staged_bytes, pieces):
+        self.path, self.height, self.width, self.channels, self.types, self.dst_masks = path, height, width, channels, types, dst_masks
+        self.compression, self.chunks, self.staged_bytes, self.pieces = compression, chunks, staged_bytes, pieces
+
+    def inflate(self, out):
+        """Write the post-inflate bytes of every chunk into `out` (a uint8 array of at least staged_bytes) at the chunks' offsets: a coded
+        chunk as deflate / the run-length coder saw it, a raw one as it is.  Raises what read_exr raises for a chunk of the wrong size."""
+        for record, (data, coded, expected) in zip(self.chunks, self.pieces):
+            if not coded:
+                t = data
+            elif self.compression == RLE_COMPRESSION:
+                t = _rle_decode(bytes(data), expected)
+            else:
+                t = zlib.decompress(data)
+                if len(t) != expected:
+                    raise ExrError("chunk expands to %d bytes, expected %d" % (len(t), expected))
+            at = int(record["offset"])
+            out[at:at + expected] = np.frombuffer(t, dtype=np.uint8)
+
+
+def _destination_masks(path, names, channels):
+    """read_image's channel choice as one destination set per file channel: R, G, B by the case-insensitive suffix after the last '.', else the
+    single channel replicated, then [..., :channels]."""
+    by_suffix = {}
+    for k, name in enumerate(names):
+        by_suffix.setdefault(name.rsplit(".", 1)[-1].upper(), k)
+    masks = [0] * len(names)
+    if all(c in by_suffix for c in "RGB"):
+        for d, c in enumerate("RGB"[:channels]):
+            masks[by_suffix[c]] |= 1 << d
+    elif len(names) == 1:
+        masks[0] = (1 << channels) - 1
+    else:
+        raise ExrError("%s: no R, G, B channels among %s" % (path, sorted(set(names))))
+    return masks
+
+
+def plan_file(path, channels=3):
+    """The host half of a device decode of `path` into the plane read_image(path)[..., :channels]: header, offset table and chunk checks of
+    read_exr (the same ExrError texts), no inflate yet and no device.  -> FilePlan."""
+    if channels < 1:
+        raise ValueError("channels=%d" % channels)
+    channels = min(int(channels), 3)
+    with open(path, "rb") as f:
+        buf = f.read()
+    try:
+        head, pos = _parse_header(buf)
+    except (ValueError, struct.error, IndexError) as e:
+        raise ExrError("%s: truncated or malformed header (%s)" % (path, e))
+    x0, y0, x1, y1 = head["data_window"]
+    W, H = x1 - x0 + 1, y1 - y0 + 1
+    if W < 1 or H < 1:
+        raise ExrError("%s: empty data window (%d x %d)" % (path, W, H))
+    chans = head["channels"]
+    if len(chans) > MAX_FILE_CHANNELS:
+        raise ExrError("%s: %d channels; the device decoder takes at most %d" % (path, len(chans), MAX_FILE_CHANNELS))
+    compression = head["compression"]
+    lines = _LINES[compression]
+    n_chunks = (H + lines - 1) // lines
+    if pos + 8 * n_chunks > len(buf):
+        raise ExrError("%s: truncated offset table" % path)
+    offsets = struct.unpack_from("<%dQ" % n_chunks, buf, pos)
+    row_bytes = sum(W * _PIXEL[t].itemsize for _, t in chans)
+    view = memoryview(buf)
+    records, pieces, at = np.zeros(n_chunks, dtype=CHUNK_DTYPE), [], 0
+    for k, off in enumerate(offsets):
+        if off + 8 > len(buf):
+            raise ExrError("%s: chunk offset %d past the end of the file" % (path, off))
+        y, size = struct.unpack_from("<ii", buf, off)
+        r0 = y - y0
+        nl = min(lines, H - r0)
+        if r0 < 0 or nl <= 0 or off + 8 + size > len(buf):
+            raise ExrError("%s: bad chunk (y %d, %d bytes)" % (path, y, size))
+        expected = nl * row_bytes
+        coded = size != expected                                # (as _decode_chunk: a chunk of the full size is stored raw)
+        if coded and compression == NO_COMPRESSION:
+            raise ExrError("chunk of %d bytes where %d are expected" % (size, expected))
+        records[k] = (at, 0, r0, nl, int(coded))
+        pieces.append((view[off + 8:off + 8 + size], coded, expected))
+        at += _align(expected)
+    masks = _destination_masks(path, [name for name, _ in chans], channels)
+    return FilePlan(path, H, W, channels, [t for _, t in chans], masks, compression, records, at, pieces)
+
+
+class DeviceDecoder:
+    """EXR files to fp32 device planes, bit-identical to read_image(path)[..., :channels]: the host inflates on `threads` threads (at most 16)
+    into a ring of two pinned buffers, each batch of files is uploaded once and rebuilt by one dd_exr_reconstruct launch, and the inflate of a
+    batch overlaps the upload and the launch of the one before.  A batch holds files whose staged bytes stay under `max_staged_bytes` (a
+    larger file goes alone)."""
+    RING = 2
+    time_launches = False                                       # measurements: keep (start, end) events around every launch in `events`
+
+    def __init__(self, device, max_staged_bytes=256 << 20, threads=4):
+        import torch
+        self.device = torch.device(device)
+        if self.device.type != "cuda":
+            raise ValueError("EXR files are decoded on a GPU: %s is none" % (self.device,))
+        if self.device.index is None:
+            self.device = torch.device("cuda", torch.cuda.current_device())
+        self.max_staged_bytes = max(int(max_staged_bytes), _STAGE_ALIGN)
+        self.threads = max(1, min(int(threads), 16))
+        self._pinned = [None] * self.RING                       # [pinned uint8 tensor, the event after its upload]
+        self._staged = None                                     # the device copy; batches follow one another on one stream
+        self.launches = 0
+        self.inflate_seconds = 0.0                              # wall time decode() spent waiting for the inflate threads
+        self.events = []
+
+    def _buffers(self, slot, nbytes):
+        import torch
+        entry = self._pinned[slot]
+        if entry is not None and entry[1] is not None:
+            entry[1].synchronize()                              # (the upload out of this buffer, RING batches ago)
+        if entry is None or entry[0].numel() < nbytes:
+            entry = self._pinned[slot] = [torch.empty(nbytes, dtype=torch.uint8, pin_memory=True), None]
+        if self._staged is None or self._staged.numel() < nbytes:
+            self._staged = torch.empty(nbytes, dtype=torch.uint8, device=self.device)      # (the caching allocator keeps the old one alive for
+        return entry                                                                      #  the launches that still read it)
+
+    def release(self):
+        """Give the pinned ring and the device staging buffer back (the counters stay)."""
+        import torch
+        torch.cuda.synchronize(self.device)
+        self._pinned, self._staged = [None] * self.RING, None
+
+    def decode(self, requests, errors="raise"):
+        """requests: [(path, channels), ...] -> [(tensor [H, W, channels] fp32 on the device, non-finite count), ...] in input order; one
+        synchronisation, at the end, to read the counts.  errors 'raise': the ExrError of the first file (in input order) that has one;
+        'return': that file's place in the list holds its ExrError and the others are decoded."""
+        import concurrent.futures
+        import time
+
+        import torch
+
+        from . import _lib as L
+        lib = L.load()
+        requests = [(p, int(c)) for p, c in requests]
+        results = [None] * len(requests)
+        with concurrent.futures.ThreadPoolExecutor(max_workers=self.threads) as pool, torch.cuda.device(self.device):
+            stream = torch.cuda.current_stream(self.device)
+
+            def plan(request):
+                try:
+                    return plan_file(*request)
+                except ExrError as e:
+                    return e
+            plans = list(pool.map(plan, requests))
+            for k, p in enumerate(plans):
+                if isinstance(p, ExrError):
+                    results[k] = p
+            good = [k for k, p in enumerate(plans) if not isinstance(p, ExrError)]
+            batches, room = [], 0
+            for k in good:
+                if not batches or room + plans[k].staged_bytes > self.max_staged_bytes:
+                    batches.append([])
+                    room = 0
+                batches[-1].append(k)
+                room += plans[k].staged_bytes
+            planes, counted = {}, []
+            for b, batch in enumerate(batches):
+                # ---- layout of the batch's buffer: staged bytes | chunk table | file table
+                bases, at = [], 0
+                for k in batch:
+                    bases.append(at)
+                    at += plans[k].staged_bytes
+                staged_bytes = max(at, _STAGE_ALIGN)
+                n_chunks = sum(len(plans[k].chunks) for k in batch)
+                chunks_at = _align(staged_bytes)
+                files_at = _align(chunks_at + n_chunks * CHUNK_DTYPE.itemsize)
+                total = files_at + len(batch) * FILE_DTYPE.itemsize
+                entry = self._buffers(b % self.RING, total)
+                host = entry[0].numpy()
+                # ---- inflate, one job per file
+                t0 = time.perf_counter()
+                jobs = [pool.submit(plans[k].inflate, host[base:base + plans[k].staged_bytes]) for k, base in zip(batch, bases)]
+                failed = set()
+                for k, job in zip(batch, jobs):
+                    try:
+                        job.result()
+                    except ExrError as e:
+                        results[k] = e
+                        failed.add(k)
+                self.inflate_seconds += time.perf_counter() - t0
+                # ---- the tables (a file that failed keeps its bytes in the buffer and gets neither a record nor a chunk)
+                live = [(k, base) for k, base in zip(batch, bases) if k not in failed]
+                chunk_table = host[chunks_at:chunks_at + n_chunks * CHUNK_DTYPE.itemsize].view(CHUNK_DTYPE)
+                file_table = host[files_at:files_at + len(batch) * FILE_DTYPE.itemsize].view(FILE_DTYPE)
+                file_table[:] = np.zeros((), dtype=FILE_DTYPE)
+                n = 0
+                for slot, (k, base) in enumerate(live):
+                    p = plans[k]
+                    planes[k] = torch.empty((p.height, p.width, p.channels), dtype=torch.float32, device=self.device)
+                    row = file_table[slot]
+                    row["dst"], row["H"], row["W"], row["C"], row["n_channels"] = planes[k].data_ptr(), p.height, p.width, p.channels, len(p.types)
+                    row["type"][:len(p.types)] = p.types
+                    row["dst_mask"][:len(p.types)] = p.dst_masks
+                    part = chunk_table[n:n + len(p.chunks)]
+                    part[:] = p.chunks
+                    part["offset"] += base
+                    part["file"] = slot
+                    n += len(p.chunks)
+                if n:
+                    dev = self._staged[:total]
+                    dev.copy_(entry[0][:total], non_blocking=True)
+                    entry[1] = torch.cuda.Event()
+                    entry[1].record(stream)
+                    if self.time_launches:
+                        self.events.append((torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)))
+                        self.events[-1][0].record(stream)
+                    slot_counts = torch.zeros(len(live), dtype=torch.int64, device=self.device)
+                    L.check(lib.dd_exr_reconstruct(host[chunks_at:].ctypes.data, dev.data_ptr() + chunks_at, n,
+                                                   host[files_at:].ctypes.data, dev.data_ptr() + files_at, len(live),
+                                                   dev.data_ptr(), staged_bytes, slot_counts.data_ptr(), stream.cuda_stream))
+                    if self.time_launches:
+                        self.events[-1][1].record(stream)
+                    counted.append(([k for k, _ in live], slot_counts))
+                    self.launches += 1
+            if counted:
+                counts = torch.cat([c for _, c in counted]).cpu().numpy()      # the one synchronisation
+                order = [k for batch, _ in counted for k in batch]
+                for k, count in zip(order, counts.tolist()):
+                    results[k] = (planes[k], int(count))
+        if errors == "raise":
+            for r in results:
+                if isinstance(r, ExrError):
+                    raise r
+        return results
+
+
 # ---------------------------------------------------------------------------------------------------- a directory of render passes
 class OpenEXRDirectory:
     """One rendered frame: a directory with one .exr per render pass, matched by '_<Pass>_' in the file name (the underscores keep
@@ -314,38 +562,55 @@ class OpenEXRDirectory:
 
 
 # ---------------------------------------------------------------------------------------------------- a frame for the Predictor
-def load_frame(directory, architecture):
+def load_frame(directory, architecture, device=None):
     """The feature dictionary Prediction.main builds from a directory of .exr files (Prediction.py:223-252): one [H,W,C] float32 array
     per required feature under 'source_image/0/<Pass>'.  Passes that are not loaded (`load_data` false) are constant 1.0 (colour) or
     0.5 (direct / indirect).  A pass's file is the one whose name contains '_<Pass>_'; the reference's looser rule -- the first
-    listed file whose path contains the pass name -- is the fallback, made deterministic by taking the shortest such name."""
+    listed file whose path contains the pass name -- is the fallback, made deterministic by taking the shortest such name.
+    With a `device` every pass is a tensor on it: the files are decoded there by one DeviceDecoder.decode call (the same values)."""
     from .naming import Naming
     frame = OpenEXRDirectory(directory)
     files = frame.exr_files()
     features, size = {}, None
     required = list(architecture.auxiliary_features) + list(architecture.feature_predictions)
-    for f in required:
-        if not f.load_data:
-            continue
+    loaded = [f for f in required if f.load_data]
+
+    def file_of(f):
         try:
-            path = frame.file_of(f.name)
+            return frame.file_of(f.name)
         except ExrError:
             loose = sorted((p for p in files if f.name in os.path.basename(p)), key=lambda p: (len(os.path.basename(p)), p))
             if not loose:
                 raise ExrError("image for '%s' could not be loaded or does not exist in %s" % (f.name, directory))
-            path = loose[0]
-        image = read_image(path)
+            return loose[0]
+
+    def on_host():
+        for f in loaded:
+            path = file_of(f)
+            yield f, path, read_image(path)[..., :f.number_of_channels]
+
+    def on_device():
+        paths = [file_of(f) for f in loaded]
+        decoded = DeviceDecoder(device).decode([(path, f.number_of_channels) for f, path in zip(loaded, paths)])
+        for f, path, (image, _) in zip(loaded, paths, decoded):
+            yield f, path, image
+    for f, path, image in (on_host() if device is None else on_device()):
         if size is None:
-            size = image.shape[:2]
-        elif size != image.shape[:2]:
+            size = tuple(image.shape[:2])
+        elif size != tuple(image.shape[:2]):
             raise ExrError("%s is %dx%d, the other passes are %dx%d" % (path, image.shape[1], image.shape[0], size[1], size[0]))
-        features[Naming.source_feature_name(f.name, index=0)] = image[..., :f.number_of_channels]
+        features[Naming.source_feature_name(f.name, index=0)] = image
     if size is None:
         raise ExrError("no pass of the architecture is loaded from files")
     for f in required:
         if not f.load_data:
             value = 1.0 if f.feature_prediction_type == "COLOR" else 0.5        # Prediction.py:244-249
-            features[Naming.source_feature_name(f.name, index=0)] = np.full(size + (f.number_of_channels,), value, dtype=np.float32)
+            shape = size + (f.number_of_channels,)
+            if device is None:
+                features[Naming.source_feature_name(f.name, index=0)] = np.full(shape, value, dtype=np.float32)
+            else:
+                import torch
+                features[Naming.source_feature_name(f.name, index=0)] = torch.full(shape, value, dtype=torch.float32, device=device)
     return features
 
 

@@ -38,6 +38,8 @@ def parser():
     p.add_argument("--blend_width", type=int, default=None,
                    help="--tile_blend feather: pixels over which a tile's weight ramps at a side that faces another tile (default: twice the overlap; "
                         "0: plain average; at most half a tile)")
+    p.add_argument("--exr_decode", default="host", choices=["host", "device"],
+                   help="Where the input EXR files are decoded: on the host, or inflated on the host and rebuilt on the device by one launch.")
     p.add_argument("--target", type=str, default=None,
                    help="directory with the ground-truth render of the frame (one .exr per pass): score every denoised pass and Combined against it on "
                         "the device, print one line per pass and write quality.json")
@@ -91,7 +93,7 @@ def main(args):
     aj = json.load(open(args.json_filename))
     assert os.path.isdir(args.input)
     arch = Architecture(aj, source_data_format="channels_last", data_format=args.data_format, device="cuda", dtype=args.dtype)
-    feats = openexr.load_frame(args.input, arch)                                   # Prediction.py:223-252
+    feats = openexr.load_frame(args.input, arch, device=arch.device if args.exr_decode == "device" else None)      # Prediction.py:223-252
     first = next(iter(feats.values()))
     height, width = first.shape[0], first.shape[1]
     mode = args.nonfinite
@@ -104,7 +106,7 @@ def main(args):
     if latest is None:
         raise SystemExit("no checkpoint in %s (train first: python -m deepdenoiser_amd.train ...)" % model_dir)
     tf_checkpoint.load_variables(arch, latest, load_optimizer=False)               # Prediction.py:497-505 restores the Estimator's latest checkpoint
-    frame = {k: torch.from_numpy(np.ascontiguousarray(v)) for k, v in feats.items()}
+    frame = {k: v if torch.is_tensor(v) else torch.from_numpy(np.ascontiguousarray(v)) for k, v in feats.items()}
     try:
         out = predictor.predict_frame(frame)
     except ValueError:

@@ -876,6 +876,37 @@ typedef struct { int n_passes; int n_planes; const int* plane_hw; const int* cel
 int dd_importance_update(const dd_importance_update_desc* desc, const dd_tile_record* records, int B, int T, int G, int use_flip, int use_rotate,
                          unsigned long long* acc_sum, unsigned int* acc_count, dd_stream stream);
 
+/* ---- OpenEXR scan-line chunks rebuilt on the device (csrc/dd_exr_decode.hip).  Replaces the decode the reference leaves to OpenCV
+ * (OpenEXRDirectory.py:125-151: cv2.imdecode of the file's bytes, BGR -> RGB, float32) and everything deepdenoiser_amd/openexr.py's host
+ * reader does after inflate: the host parses the header and the offset table and inflates (or run-length decodes) each chunk into ONE staged
+ * buffer for a whole batch of files; ONE launch then undoes the byte predictor and the even / odd byte split of every coded chunk, splits rows
+ * and channels, converts UINT / HALF / FLOAT samples to fp32, writes the [H, W, C] fp32 planes and counts the non-finite samples per file.
+ * The planes are bit-identical to openexr.read_image(path)[..., :C].
+ *   chunk   : n = rows * row_bytes bytes at `offset` of the staged buffer (16-byte aligned; the chunk owns the bytes up to the next multiple
+ *             of 16), row_bytes = sum over the file's channels of W * sample size; rows row0 .. row0 + rows - 1 of file `file`.  coded != 0:
+ *             the bytes t are as deflate / the run-length coder saw them -- s[i] = (t[0] + sum_{j=1..i} (t[j] - 128)) & 0xFF in place, then
+ *             the original byte p is s[p >> 1] (p even) or s[(n + 1) / 2 + (p >> 1)] (p odd).  coded == 0: the bytes are original
+ *             (NO_COMPRESSION, or a chunk stored raw because coding did not shrink it).  Within a row the file's channels follow one another
+ *             in header order, W samples each; one workgroup of 256 threads per chunk, a chunk need not fit LDS.
+ *   file    : dst fp32 [H, W, C] contiguous; per file channel c < n_channels its pixel type (0 UINT: (float)u rounded to nearest even, 1 HALF:
+ *             widened exactly, subnormals included, 2 FLOAT: the bits are moved) and dst_mask[c], the set of destination channels it is
+ *             written to (bit d = channel d of dst): 0 for a channel that is skipped (A of an RGBA file), several bits for the single channel
+ *             of a file that read_image replicates.  A destination channel no mask names is not written.
+ *   counts  : DEVICE uint64[n_files], zeroed by the caller: counts[file] += the destination samples written whose value is NaN or +-Inf
+ *             (== np.count_nonzero(~np.isfinite(plane))); one integer atomic add per workgroup.
+ * Both tables are given twice: the HOST copy is validated here, the DEVICE copy is what the kernel reads -- and, because it cannot trust
+ * device memory, checks again: a chunk whose file index is out of range, whose rows fall outside [0, H) or whose bytes leave the staged
+ * buffer is skipped, so nothing is written outside a plane.
+ * Refused with a negative status and no launch: NULL tables or buffers while n_chunks > 0, n_chunks < 0, rows outside 1 .. 16, a file with 0
+ * or more than DD_EXR_MAX_CHANNELS channels, a pixel type outside 0 .. 2, W < 1 or H < 1, C outside 1 .. 32, a destination channel >= C, a
+ * chunk whose file index or rows do not fit its file, an offset that is not 16-byte aligned or leaves staged_bytes.  n_chunks == 0 is a no-op
+ * that returns 0.  No host sync. */
+#define DD_EXR_MAX_CHANNELS 8
+typedef struct { long long offset; int file; int row0; int rows; int coded; } dd_exr_chunk;
+typedef struct { float* dst; int H; int W; int C; int n_channels; int type[DD_EXR_MAX_CHANNELS]; unsigned int dst_mask[DD_EXR_MAX_CHANNELS]; } dd_exr_file;
+int dd_exr_reconstruct(const dd_exr_chunk* chunks_host, const dd_exr_chunk* chunks, int n_chunks, const dd_exr_file* files_host,
+                       const dd_exr_file* files, int n_files, void* staged, long staged_bytes, unsigned long long* counts, dd_stream stream);
+
 /* 3x3/s2 transpose conv (Tiramisu.py:62-64) = 3x3 SAME conv of the zero-stuffed input with the flipped kernel:
  * y[B,2H,2W,C] = 0 except y[2i+1,2j+1] = x[i,j]; and its adjoint dx[i,j] (+)= dy[2i+1,2j+1] * (mask>0). */
 int dd_zero_stuff(const void* x, int ldx, void* y, int ldy, int C, int B, int H, int W, int dtype, dd_stream stream);
