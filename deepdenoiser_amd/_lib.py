@@ -51,7 +51,7 @@ SYMBOLS = (
     "dd_histogram_values", "dd_loss_histograms_scratch_bytes", "dd_loss_histograms", "dd_loss_previews",
     "dd_nonfinite_scan", "dd_nonfinite_repair", "dd_frame_quality_scratch_bytes", "dd_frame_quality", "dd_stitch_blend",
     "dd_grad_norms", "dd_adam_step_clipped", "dd_adam_step_scaled_clipped", "dd_sample_tiles",
-    "dd_tile_statistics", "dd_importance_cells", "dd_importance_update", "dd_exr_reconstruct",
+    "dd_tile_statistics", "dd_importance_cells", "dd_importance_update", "dd_exr_reconstruct", "dd_exr_inflate",
 )
 
 
@@ -281,6 +281,16 @@ class ExrFile(C.Structure):            # dd_exr_file: the plane a file is decode
                 ("type", C.c_int * EXR_MAX_CHANNELS), ("dst_mask", C.c_uint * EXR_MAX_CHANNELS)]
 
 
+class ExrStream(C.Structure):          # dd_exr_stream: one zlib stream of dd_exr_inflate and where its bytes go in the staged buffer (24 bytes)
+    _fields_ = [("src_offset", C.c_longlong), ("dst_offset", C.c_longlong), ("src_bytes", C.c_int), ("dst_bytes", C.c_int)]
+
+
+# DD_INFLATE_*: the per-stream status codes of dd_exr_inflate
+(INFLATE_OK, INFLATE_HEADER, INFLATE_TRUNCATED, INFLATE_BLOCK_TYPE, INFLATE_STORED, INFLATE_LENGTHS, INFLATE_SYMBOL, INFLATE_DISTANCE,
+ INFLATE_OVERRUN, INFLATE_SHORT, INFLATE_CHECK, INFLATE_RECORD) = range(12)
+INFLATE_STATUS_NAMES = ("OK", "HEADER", "TRUNCATED", "BLOCK_TYPE", "STORED", "LENGTHS", "SYMBOL", "DISTANCE", "OVERRUN", "SHORT", "CHECK", "RECORD")
+
+
 class StitchEntry(C.Structure):
     _fields_ = [("tile", C.c_int), ("crop_y0", C.c_int), ("crop_y1", C.c_int), ("crop_x0", C.c_int),
                 ("crop_x1", C.c_int), ("dst_img", C.c_int), ("dst_y", C.c_int), ("dst_x", C.c_int)]
@@ -482,6 +492,7 @@ def load():
     lib.dd_importance_cells.argtypes = [C.POINTER(ImportanceDesc), vp, i, i, vp, vp]
     lib.dd_importance_update.argtypes = [C.POINTER(ImportanceUpdateDesc), vp, i, i, i, i, i, vp, vp, vp]
     lib.dd_exr_reconstruct.argtypes = [vp, vp, i, vp, vp, i, vp, l, vp, vp]
+    lib.dd_exr_inflate.argtypes = [vp, vp, i, vp, l, vp, l, vp, vp]
     _lib = lib
     return lib
 

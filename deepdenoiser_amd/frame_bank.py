@@ -136,9 +136,10 @@ class FrameBank:
     pointers[name]: the same as a device int64 array (0 where None); plane_hw: device int32 [n_planes, 2]; hw: the same on the host.
     A scene with a non-finite sample is skipped with one line through `log` (OpenEXRDirectory.py:72-76).
     decode: 'host' -- every file goes through openexr.read_image on `threads` threads and is uploaded; 'device' -- the host only inflates and
-    one dd_exr_reconstruct launch per scene rebuilds the planes on the device (openexr.DeviceDecoder): the same planes, bit for bit."""
+    one dd_exr_reconstruct launch per scene rebuilds the planes on the device (openexr.DeviceDecoder): the same planes, bit for bit.
+    inflate: with decode 'device', 'device' -- the host only reads the files and a dd_exr_inflate launch per scene inflates them."""
 
-    def __init__(self, arch, frame_set, spp=None, device=None, memory_limit_bytes=None, threads=4, log=print, decode="host"):
+    def __init__(self, arch, frame_set, spp=None, device=None, memory_limit_bytes=None, threads=4, log=print, decode="host", inflate="host"):
         self.frame_set, self.tile, self.S = frame_set, frame_set.tile, frame_set.number_of_sources_per_example
         self.spp = int(frame_set.source_spps[0] if spp is None else spp)
         self.device = torch.device(arch.device if device is None else device)
@@ -150,14 +151,14 @@ class FrameBank:
             for name in need:
                 if name not in have:
                     raise ValueError("the architecture loads the %s pass '%s', which the frame set's %s features do not list" % (what, name, what))
-        self._load(frame_set.scenes, memory_limit_bytes, threads, log, decode)
+        self._load(frame_set.scenes, memory_limit_bytes, threads, log, decode, inflate)
         if not self.scenes:
             raise ValueError("no usable scene is left (%d skipped)" % (len(frame_set.skipped) + len(self.skipped)))
         self._tables()
 
     @classmethod
     def for_passes(cls, frame_set, source_channels, target_channels, spp, scenes=None, device="cuda", memory_limit_bytes=None, threads=4, log=print,
-                   decode="host"):
+                   decode="host", inflate="host"):
         """A bank of the passes `source_channels` / `target_channels` ({pass name: channels}) without an Architecture: what the data-set
         statistics read (deepdenoiser_amd/statistics.py).  `spp`: one samples-per-pixel count or a list of them -- with a list a scene owns
         len(spp) * S source planes, those of the first count first, and `S` is that product, so source_plane / target_plane hold.  `scenes`:
@@ -170,16 +171,20 @@ class FrameBank:
                 raise ValueError("%d samples per pixel: the frame set lists %s" % (s, frame_set.source_spps))
         self.spp, self.S = self.spps[0], frame_set.number_of_sources_per_example * len(self.spps)
         self.source_channels, self.target_channels = dict(source_channels), dict(target_channels)
-        self._load(frame_set.scenes if scenes is None else scenes, memory_limit_bytes, threads, log, decode)
+        self._load(frame_set.scenes if scenes is None else scenes, memory_limit_bytes, threads, log, decode, inflate)
         self._tables()
         return self
 
-    def _load(self, scenes, memory_limit_bytes, threads, log, decode="host"):
+    def _load(self, scenes, memory_limit_bytes, threads, log, decode="host", inflate="host"):
         if decode not in ("host", "device"):
             raise ValueError("decode: 'host' or 'device', not %r" % (decode,))
-        self.decode = decode
+        if inflate not in ("host", "device"):
+            raise ValueError("inflate: 'host' or 'device', not %r" % (inflate,))
+        if inflate == "device" and decode != "device":
+            raise ValueError("inflate='device' needs decode='device': the device inflates into the staged buffer of the device decoder")
+        self.decode, self.inflate = decode, inflate
         # (a decoder refuses a device that is no GPU with ValueError, before anything is read)
-        decoder = openexr.DeviceDecoder(self.device, threads=max(1, min(int(threads), 16))) if decode == "device" else None
+        decoder = openexr.DeviceDecoder(self.device, threads=max(1, min(int(threads), 16)), inflate=inflate) if decode == "device" else None
         # ---- the bytes, before anything is allocated
         per_pixel = 4 * (self.S * sum(self.source_channels.values()) + sum(self.target_channels.values()))
         self.total_bytes = sum(s.height * s.width * per_pixel for s in scenes)

@@ -277,12 +277,16 @@ def write_image(path, image, compression=ZIP_COMPRESSION):
 
 # ---------------------------------------------------------------------------------------------------- decode on the device
 # The host keeps the header, the offset table and inflate (zlib releases the GIL); the predictor, the byte split, the row / channel split and
-# the conversion to fp32 are one dd_exr_reconstruct launch over the staged bytes of many files (csrc/dd_exr_decode.hip).
+# the conversion to fp32 are one dd_exr_reconstruct launch over the staged bytes of many files (csrc/dd_exr_decode.hip).  With
+# inflate="device" the host keeps only the header, the offset table and the run-length decode: one dd_exr_inflate launch per batch
+# (csrc/dd_exr_inflate.hip) expands the zlib streams of the ZIP / ZIPS chunks into the staged buffer on the device.
 _STAGE_ALIGN = 16                                               # a chunk's offset in the staged buffer; it owns the bytes up to the next multiple
 CHUNK_DTYPE = np.dtype([("offset", "<i8"), ("file", "<i4"), ("row0", "<i4"), ("rows", "<i4"), ("coded", "<i4")])      # dd_exr_chunk
 FILE_DTYPE = np.dtype([("dst", "<u8"), ("H", "<i4"), ("W", "<i4"), ("C", "<i4"), ("n_channels", "<i4"), ("type", "<i4", (8,)),
                        ("dst_mask", "<u4", (8,))])                                                                       # dd_exr_file
 MAX_FILE_CHANNELS = 8                                           # DD_EXR_MAX_CHANNELS
+STREAM_DTYPE = np.dtype([("src_offset", "<i8"), ("dst_offset", "<i8"), ("src_bytes", "<i4"), ("dst_bytes", "<i4")])      # dd_exr_stream
+MAX_STREAM_BYTES = 1 << 30                                      # dd_exr_inflate refuses a stream that expands to more
 
 
 def _align(n):
@@ -298,6 +302,7 @@ class FilePlan:
     def __init__(self, path, height, width, channels, types, dst_masks, compression, chunks, staged_bytes, pieces):
         self.path, self.height, self.width, self.channels, self.types, self.dst_masks = path, height, width, channels, types, dst_masks
         self.compression, self.chunks, self.staged_bytes, self.pieces = compression, chunks, staged_bytes, pieces
+        self._source = None
 
     def inflate(self, out):
         """Write the post-inflate bytes of every chunk into `out` (a uint8 array of at least staged_bytes) at the chunks' offsets: a coded
@@ -313,6 +318,104 @@ class FilePlan:
                     raise ExrError("chunk expands to %d bytes, expected %d" % (len(t), expected))
             at = int(record["offset"])
             out[at:at + expected] = np.frombuffer(t, dtype=np.uint8)
+
+
+    def source_layout(self):
+        """What inflate="device" uploads of this file instead of its inflated image -> (source_bytes, streams, runs, places, refused).
+        The zlib stream of every coded ZIP / ZIPS chunk is packed as it is in the file: `streams` are STREAM_DTYPE records, src_offset
+        relative to the file's source bytes, dst_offset to its staged bytes.  Every other chunk -- stored raw, or run-length coded (the host
+        keeps _rle_decode) -- is `plain`: its post-inflate bytes go into the source bytes, and a run of consecutive plain chunks is laid out
+        there exactly as in the staged image (16-byte aligned pieces), so that ONE device copy per run moves it to its place: `runs` are
+        (source offset, staged offset, bytes).  places: per chunk its offset in the source bytes.  refused: a stream dd_exr_inflate does not
+        take (no bytes, or more than MAX_STREAM_BYTES to write); such a file is left to the host path."""
+        if self._source is None:
+            zipped = self.compression in (ZIP_COMPRESSION, ZIPS_COMPRESSION)
+            streams, runs, places, at, refused, plain_before = [], [], [], 0, False, False
+            for record, (data, coded, expected) in zip(self.chunks, self.pieces):
+                dst = int(record["offset"])
+                if coded and zipped:
+                    refused = refused or len(data) < 1 or expected > MAX_STREAM_BYTES
+                    places.append(at)
+                    streams.append((at, dst, len(data), expected))
+                    at += len(data)
+                    plain_before = False
+                else:
+                    if not plain_before:
+                        at = _align(at)
+                        runs.append([at, dst, 0])
+                    places.append(at)
+                    runs[-1][2] += _align(expected)
+                    at += _align(expected)
+                    plain_before = True
+            table = np.zeros(len(streams), dtype=STREAM_DTYPE)
+            if streams and not refused:
+                table[:] = streams
+            self._source = (at, table, [tuple(r) for r in runs], places, refused)
+        return self._source
+
+    def fill_source(self, out):
+        """Write the source bytes of source_layout() into `out` (a uint8 array of at least that many): copies, and the run-length decode.
+        Raises what inflate() raises for a run-length coded chunk of the wrong size."""
+        zipped = self.compression in (ZIP_COMPRESSION, ZIPS_COMPRESSION)
+        for at, (data, coded, expected) in zip(self.source_layout()[3], self.pieces):
+            t = _rle_decode(bytes(data), expected) if coded and not zipped else data
+            out[at:at + len(t)] = np.frombuffer(t, dtype=np.uint8)
+
+
+def _batch_layout(plans):
+    """the arithmetic of pack_batch: where everything lies"""
+    source_bases, staged_bases, source_at, staged_at = [], [], 0, 0
+    for p in plans:
+        source_bases.append(source_at)
+        staged_bases.append(staged_at)
+        source_at = _align(source_at + p.source_layout()[0])
+        staged_at += p.staged_bytes
+    n_streams = sum(len(p.source_layout()[1]) for p in plans)
+    n_chunks = sum(len(p.chunks) for p in plans)
+    layout = {"source_bases": source_bases, "staged_bases": staged_bases, "source_bytes": max(source_at, _STAGE_ALIGN),
+              "staged_bytes": max(staged_at, _STAGE_ALIGN), "n_streams": n_streams, "n_chunks": n_chunks}
+    layout["streams_at"] = _align(layout["source_bytes"])
+    layout["chunks_at"] = _align(layout["streams_at"] + n_streams * STREAM_DTYPE.itemsize)
+    layout["files_at"] = _align(layout["chunks_at"] + n_chunks * CHUNK_DTYPE.itemsize)
+    layout["total"] = layout["files_at"] + len(plans) * FILE_DTYPE.itemsize
+    layout["runs"] = [(src + sb, dst + db, n) for p, sb, db in zip(plans, source_bases, staged_bases) for src, dst, n in p.source_layout()[2]]
+    layout["owners"] = [k for k, p in enumerate(plans) for _ in range(len(p.source_layout()[1]))]
+    return layout
+
+
+def pack_batch(plans):
+    """The upload buffer of one batch of inflate="device", in plain numpy (DeviceDecoder lays its pinned buffer out the same way):
+    source bytes of every file | stream table | chunk table.  -> (buffer uint8, layout) with layout = {"source_bases", "staged_bases",
+    "source_bytes", "staged_bytes", "streams_at", "n_streams", "chunks_at", "n_chunks", "files_at", "total", "runs": [(source offset,
+    staged offset, bytes)] of the whole batch, "owners": per stream the index of its plan}.  The file table's place is reserved; its rows hold
+    device pointers and are written by the decoder."""
+    layout = _batch_layout(plans)
+    buffer = np.zeros(layout["total"], dtype=np.uint8)
+    fill_batch_tables(buffer, layout, plans)
+    for p, base in zip(plans, layout["source_bases"]):
+        p.fill_source(buffer[base:base + p.source_layout()[0]])
+    return buffer, layout
+
+
+def fill_batch_tables(buffer, layout, plans):
+    """The stream and the chunk table of pack_batch's layout, written into `buffer`: offsets made absolute, a chunk's `file` the index of
+    its plan."""
+    streams = buffer[layout["streams_at"]:layout["streams_at"] + layout["n_streams"] * STREAM_DTYPE.itemsize].view(STREAM_DTYPE)
+    chunks = buffer[layout["chunks_at"]:layout["chunks_at"] + layout["n_chunks"] * CHUNK_DTYPE.itemsize].view(CHUNK_DTYPE)
+    ns = nc = 0
+    for slot, (p, source_base, staged_base) in enumerate(zip(plans, layout["source_bases"], layout["staged_bases"])):
+        table = p.source_layout()[1]
+        part = streams[ns:ns + len(table)]
+        part[:] = table
+        part["src_offset"] += source_base
+        part["dst_offset"] += staged_base
+        ns += len(table)
+        part = chunks[nc:nc + len(p.chunks)]
+        part[:] = p.chunks
+        part["offset"] += staged_base
+        part["file"] = slot
+        nc += len(p.chunks)
+    return streams, chunks
 
 
 def _destination_masks(path, names, channels):
@@ -383,13 +486,23 @@ class DeviceDecoder:
     """EXR files to fp32 device planes, bit-identical to read_image(path)[..., :channels]: the host inflates on `threads` threads (at most 16)
     into a ring of two pinned buffers, each batch of files is uploaded once and rebuilt by one dd_exr_reconstruct launch, and the inflate of a
     batch overlaps the upload and the launch of the one before.  A batch holds files whose staged bytes stay under `max_staged_bytes` (a
-    larger file goes alone)."""
+    larger file goes alone).
+    inflate="device": the host only reads the files.  A batch's pinned buffer holds the zlib streams of the coded ZIP / ZIPS chunks as they
+    are in the files, the bytes of raw chunks and the run-length decoded bytes of RLE chunks (FilePlan.source_layout), the stream table and
+    the two tables of before: about the size of the files, not of the planes.  After the one upload, one dd_exr_inflate launch expands every
+    stream into a device-only staged buffer, one device copy per run of consecutive raw / RLE chunks puts those in place, and the
+    dd_exr_reconstruct launch follows on the same stream.  The per-stream statuses are read with the counts, in the one synchronisation at
+    the end; a file with a stream that is not OK is redone through the host path (`host_fallbacks` counts them), so a corrupt file raises
+    what inflate="host" raises and a stream the device refused but zlib accepts still decodes."""
     RING = 2
     time_launches = False                                       # measurements: keep (start, end) events around every launch in `events`
+                                                                # (and around every dd_exr_inflate launch in `inflate_events`)
 
-    def __init__(self, device, max_staged_bytes=256 << 20, threads=4):
+    def __init__(self, device, max_staged_bytes=256 << 20, threads=4, inflate="host"):
         import torch
         self.device = torch.device(device)
+        if inflate not in ("host", "device"):
+            raise ValueError("inflate=%r (host or device)" % (inflate,))
         if self.device.type != "cuda":
             raise ValueError("EXR files are decoded on a GPU: %s is none" % (self.device,))
         if self.device.index is None:
@@ -398,12 +511,20 @@ class DeviceDecoder:
         self.threads = max(1, min(int(threads), 16))
         self._pinned = [None] * self.RING                       # [pinned uint8 tensor, the event after its upload]
         self._staged = None                                     # the device copy; batches follow one another on one stream
+        self._image = None                                      # inflate="device": the staged image, never on the host
+        self.inflate = inflate
         self.launches = 0
-        self.inflate_seconds = 0.0                              # wall time decode() spent waiting for the inflate threads
+        self.inflate_launches = 0
+        self.host_fallbacks = 0                                 # files redone on the host because a stream's status was not OK
+        self.uploaded_bytes = 0
+        self.inflate_seconds = 0.0                              # wall time decode() spent waiting for the host jobs (inflate, or copies + RLE)
         self.events = []
+        self.inflate_events = []
 
-    def _buffers(self, slot, nbytes):
+    def _buffers(self, slot, nbytes, image_bytes=0):
         import torch
+        if image_bytes and (self._image is None or self._image.numel() < image_bytes):
+            self._image = torch.empty(image_bytes, dtype=torch.uint8, device=self.device)
         entry = self._pinned[slot]
         if entry is not None and entry[1] is not None:
             entry[1].synchronize()                              # (the upload out of this buffer, RING batches ago)
@@ -417,7 +538,101 @@ class DeviceDecoder:
         """Give the pinned ring and the device staging buffer back (the counters stay)."""
         import torch
         torch.cuda.synchronize(self.device)
-        self._pinned, self._staged = [None] * self.RING, None
+        self._pinned, self._staged, self._image = [None] * self.RING, None, None
+
+    def _on_host(self, lib, L, plan, stream):
+        """One file through the host path on its own: plan.inflate, an upload and a dd_exr_reconstruct launch into a fresh plane with a
+        fresh count -> (plane, count).  Raises what plan.inflate raises."""
+        import torch
+        n = len(plan.chunks)
+        chunks_at = _align(max(plan.staged_bytes, _STAGE_ALIGN))
+        files_at = _align(chunks_at + n * CHUNK_DTYPE.itemsize)
+        host = np.zeros(files_at + FILE_DTYPE.itemsize, dtype=np.uint8)
+        plan.inflate(host[:plan.staged_bytes])
+        plane = torch.empty((plan.height, plan.width, plan.channels), dtype=torch.float32, device=self.device)
+        chunk_table = host[chunks_at:chunks_at + n * CHUNK_DTYPE.itemsize].view(CHUNK_DTYPE)
+        chunk_table[:] = plan.chunks
+        row = host[files_at:].view(FILE_DTYPE)[0]
+        row["dst"], row["H"], row["W"], row["C"], row["n_channels"] = plane.data_ptr(), plan.height, plan.width, plan.channels, len(plan.types)
+        row["type"][:len(plan.types)] = plan.types
+        row["dst_mask"][:len(plan.types)] = plan.dst_masks
+        dev = torch.from_numpy(host).to(self.device)
+        count = torch.zeros(1, dtype=torch.int64, device=self.device)
+        L.check(lib.dd_exr_reconstruct(host[chunks_at:].ctypes.data, dev.data_ptr() + chunks_at, n, host[files_at:].ctypes.data,
+                                       dev.data_ptr() + files_at, 1, dev.data_ptr(), chunks_at, count.data_ptr(), stream.cuda_stream))
+        self.launches += 1
+        return plane, int(count.item())
+
+    def _inflate_batch(self, lib, L, pool, stream, slot, batch, plans, results, planes):
+        """One batch of inflate="device" -> (files in table order, their counts on the device, per stream the file it belongs to, the
+        statuses on the device), or None when no file of the batch is left."""
+        import time
+
+        import torch
+        t0 = time.perf_counter()
+        failed = set()
+        live = [k for k in batch if not plans[k].source_layout()[4]]      # (a refused file is redone on the host with the failed ones)
+        layout = None
+        while live:
+            layout_plans = [plans[k] for k in live]
+            layout = _batch_layout(layout_plans)
+            entry = self._buffers(slot, layout["total"], layout["staged_bytes"])
+            host = entry[0].numpy()
+            jobs = [pool.submit(p.fill_source, host[base:base + p.source_layout()[0]]) for p, base in zip(layout_plans, layout["source_bases"])]
+            bad = set()
+            for k, job in zip(live, jobs):
+                try:
+                    job.result()
+                except ExrError as e:
+                    results[k] = e
+                    bad.add(k)
+            if not bad:
+                break
+            failed |= bad                                           # (a run-length coded chunk of the wrong size: lay the batch out without the file)
+            live = [k for k in live if k not in bad]
+        self.inflate_seconds += time.perf_counter() - t0
+        if not live:
+            return None
+        total, staged_bytes = layout["total"], layout["staged_bytes"]
+        streams, _ = fill_batch_tables(host, layout, layout_plans)
+        file_table = host[layout["files_at"]:total].view(FILE_DTYPE)
+        file_table[:] = np.zeros((), dtype=FILE_DTYPE)
+        for slot_in_table, k in enumerate(live):
+            p = plans[k]
+            planes[k] = torch.empty((p.height, p.width, p.channels), dtype=torch.float32, device=self.device)
+            row = file_table[slot_in_table]
+            row["dst"], row["H"], row["W"], row["C"], row["n_channels"] = planes[k].data_ptr(), p.height, p.width, p.channels, len(p.types)
+            row["type"][:len(p.types)] = p.types
+            row["dst_mask"][:len(p.types)] = p.dst_masks
+        dev, image = self._staged[:total], self._image[:staged_bytes]
+        dev.copy_(entry[0][:total], non_blocking=True)
+        self.uploaded_bytes += total
+        entry[1] = torch.cuda.Event()
+        entry[1].record(stream)
+        n_streams = layout["n_streams"]
+        statuses = torch.empty(n_streams, dtype=torch.int32, device=self.device)
+        if n_streams:
+            if self.time_launches:
+                self.inflate_events.append((torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)))
+                self.inflate_events[-1][0].record(stream)
+            L.check(lib.dd_exr_inflate(host[layout["streams_at"]:].ctypes.data, dev.data_ptr() + layout["streams_at"], n_streams, dev.data_ptr(),
+                                       layout["source_bytes"], image.data_ptr(), staged_bytes, statuses.data_ptr(), stream.cuda_stream))
+            if self.time_launches:
+                self.inflate_events[-1][1].record(stream)
+            self.inflate_launches += 1
+        for src, dst, n in layout["runs"]:                          # raw and run-length decoded chunks: one device copy per run
+            image[dst:dst + n].copy_(dev[src:src + n], non_blocking=True)
+        if self.time_launches:
+            self.events.append((torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)))
+            self.events[-1][0].record(stream)
+        slot_counts = torch.zeros(len(live), dtype=torch.int64, device=self.device)
+        L.check(lib.dd_exr_reconstruct(host[layout["chunks_at"]:].ctypes.data, dev.data_ptr() + layout["chunks_at"], layout["n_chunks"],
+                                       host[layout["files_at"]:].ctypes.data, dev.data_ptr() + layout["files_at"], len(live),
+                                       image.data_ptr(), staged_bytes, slot_counts.data_ptr(), stream.cuda_stream))
+        if self.time_launches:
+            self.events[-1][1].record(stream)
+        self.launches += 1
+        return live, slot_counts, [live[o] for o in layout["owners"]], statuses
 
     def decode(self, requests, errors="raise"):
         """requests: [(path, channels), ...] -> [(tensor [H, W, channels] fp32 on the device, non-finite count), ...] in input order; one
@@ -452,8 +667,15 @@ class DeviceDecoder:
                     room = 0
                 batches[-1].append(k)
                 room += plans[k].staged_bytes
-            planes, counted = {}, []
+            planes, counted, checked = {}, [], []
+            redo = [k for k in good if self.inflate == "device" and plans[k].source_layout()[4]]
             for b, batch in enumerate(batches):
+                if self.inflate == "device":
+                    done = self._inflate_batch(lib, L, pool, stream, b % self.RING, batch, plans, results, planes)
+                    if done is not None:
+                        counted.append(done[:2])
+                        checked.append(done[2:])
+                    continue
                 # ---- layout of the batch's buffer: staged bytes | chunk table | file table
                 bases, at = [], 0
                 for k in batch:
@@ -512,15 +734,40 @@ class DeviceDecoder:
                     counted.append(([k for k, _ in live], slot_counts))
                     self.launches += 1
             if counted:
-                counts = torch.cat([c for _, c in counted]).cpu().numpy()      # the one synchronisation
+                n_counts = sum(len(batch) for batch, _ in counted)
+                both = torch.cat([c for _, c in counted] + [s.to(torch.int64) for _, s in checked]).cpu().numpy()      # the one synchronisation
                 order = [k for batch, _ in counted for k in batch]
-                for k, count in zip(order, counts.tolist()):
+                for k, count in zip(order, both[:n_counts].tolist()):
                     results[k] = (planes[k], int(count))
+                owners = [k for batch_owners, _ in checked for k in batch_owners]
+                redo += sorted({k for k, status in zip(owners, both[n_counts:].tolist()) if status != 0})
+            for k in sorted(redo):                                  # inflate="device": a stream that is not OK, in input order
+                self.host_fallbacks += 1
+                try:
+                    results[k] = self._on_host(lib, L, plans[k], stream)
+                except ExrError as e:
+                    results[k] = e
         if errors == "raise":
             for r in results:
                 if isinstance(r, ExrError):
                     raise r
         return results
+
+
+def add_inflate_argument(p, what):
+    """--exr_inflate on a parser that has --exr_decode: the device inflates only into the staged buffer of the device decoder, so `device`
+    without --exr_decode device is a usage error of the parser."""
+    p.add_argument("--exr_inflate", default="host", choices=["host", "device"],
+                   help="%s: with --exr_decode device, where the zlib streams of ZIP / ZIPS chunks are inflated: on the host threads, or on the "
+                        "device by one launch per batch (the host only reads the files)." % what)
+    inner = p.parse_known_args
+
+    def parse_known_args(args=None, namespace=None):
+        parsed, rest = inner(args, namespace)
+        if parsed.exr_inflate == "device" and parsed.exr_decode != "device":
+            p.error("--exr_inflate device needs --exr_decode device")
+        return parsed, rest
+    p.parse_known_args = parse_known_args
 
 
 # ---------------------------------------------------------------------------------------------------- a directory of render passes
@@ -562,12 +809,17 @@ class OpenEXRDirectory:
 
 
 # ---------------------------------------------------------------------------------------------------- a frame for the Predictor
-def load_frame(directory, architecture, device=None):
+def load_frame(directory, architecture, device=None, inflate="host"):
     """The feature dictionary Prediction.main builds from a directory of .exr files (Prediction.py:223-252): one [H,W,C] float32 array
     per required feature under 'source_image/0/<Pass>'.  Passes that are not loaded (`load_data` false) are constant 1.0 (colour) or
     0.5 (direct / indirect).  A pass's file is the one whose name contains '_<Pass>_'; the reference's looser rule -- the first
     listed file whose path contains the pass name -- is the fallback, made deterministic by taking the shortest such name.
-    With a `device` every pass is a tensor on it: the files are decoded there by one DeviceDecoder.decode call (the same values)."""
+    With a `device` every pass is a tensor on it: the files are decoded there by one DeviceDecoder.decode call (the same values);
+    inflate="device" lets that decoder inflate on the device too."""
+    if inflate not in ("host", "device"):
+        raise ValueError("inflate=%r (host or device)" % (inflate,))
+    if inflate == "device" and device is None:
+        raise ValueError("inflate='device' needs a device to decode on")
     from .naming import Naming
     frame = OpenEXRDirectory(directory)
     files = frame.exr_files()
@@ -591,7 +843,7 @@ def load_frame(directory, architecture, device=None):
 
     def on_device():
         paths = [file_of(f) for f in loaded]
-        decoded = DeviceDecoder(device).decode([(path, f.number_of_channels) for f, path in zip(loaded, paths)])
+        decoded = DeviceDecoder(device, inflate=inflate).decode([(path, f.number_of_channels) for f, path in zip(loaded, paths)])
         for f, path, (image, _) in zip(loaded, paths, decoded):
             yield f, path, image
     for f, path, image in (on_host() if device is None else on_device()):

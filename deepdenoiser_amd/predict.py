@@ -40,6 +40,7 @@ def parser():
                         "0: plain average; at most half a tile)")
     p.add_argument("--exr_decode", default="host", choices=["host", "device"],
                    help="Where the input EXR files are decoded: on the host, or inflated on the host and rebuilt on the device by one launch.")
+    openexr.add_inflate_argument(p, "--exr_decode device")
     p.add_argument("--target", type=str, default=None,
                    help="directory with the ground-truth render of the frame (one .exr per pass): score every denoised pass and Combined against it on "
                         "the device, print one line per pass and write quality.json")
@@ -93,7 +94,7 @@ def main(args):
     aj = json.load(open(args.json_filename))
     assert os.path.isdir(args.input)
     arch = Architecture(aj, source_data_format="channels_last", data_format=args.data_format, device="cuda", dtype=args.dtype)
-    feats = openexr.load_frame(args.input, arch, device=arch.device if args.exr_decode == "device" else None)      # Prediction.py:223-252
+    feats = openexr.load_frame(args.input, arch, device=arch.device if args.exr_decode == "device" else None, inflate=args.exr_inflate)      # Prediction.py:223-252
     first = next(iter(feats.values()))
     height, width = first.shape[0], first.shape[1]
     mode = args.nonfinite

@@ -1,6 +1,6 @@
 """Data-set statistics of a frame set, reduced on the device: <mode>_statistics.json without TensorFlow and without a tile set on disk.
 
-    python -m deepdenoiser_amd.statistics tfrecords.json [--mode M ...] [--output DIR] [--frame_memory_gb X] [--threads N] [--exr_decode {host,device}]
+    python -m deepdenoiser_amd.statistics tfrecords.json [--mode M ...] [--output DIR] [--frame_memory_gb X] [--threads N] [--exr_decode {host,device}] [--exr_inflate {host,device}]
 
 The reference makes the file with `python TFRecordsCreator.py tfrecords.json --statistics` (TFRecordsStatistics.py, FeatureStatistics.py): two
 sweeps over the tiles it wrote to disk, in TensorFlow 1.x eager mode.  Here the rendered EXR frames are the data set (frame_bank.py): the
@@ -167,7 +167,7 @@ class FrameStatistics:
                                             torch.cuda.current_stream(bank.device).cuda_stream))
         return rows, spp_index
 
-    def compute(self, device="cuda", memory_limit_bytes=None, threads=4, log=print, decode="host"):
+    def compute(self, device="cuda", memory_limit_bytes=None, threads=4, log=print, decode="host", inflate="host"):
         """Scenes in chunks that fit the limit (default: 80 % of the free device memory): load, launch, copy the table back, free."""
         import torch
         from .frame_bank import FrameBank
@@ -177,7 +177,7 @@ class FrameStatistics:
         rows, index = [], []
         for scenes in chunk_scenes(self.frame_set.scenes, self.bytes_per_pixel, memory_limit_bytes):
             bank = FrameBank.for_passes(self.frame_set, self.source_channels, self.target_channels, self.spps, scenes=scenes, device=device,
-                                        memory_limit_bytes=memory_limit_bytes, threads=threads, log=log, decode=decode)
+                                        memory_limit_bytes=memory_limit_bytes, threads=threads, log=log, decode=decode, inflate=inflate)
             self.skipped += bank.skipped
             if bank.scenes:
                 with torch.cuda.device(device):
@@ -249,6 +249,8 @@ def parser():
     p.add_argument("--device", default="cuda", help="The device the frames are reduced on.")
     p.add_argument("--exr_decode", default="host", choices=["host", "device"],
                    help="Where the EXR files are decoded: on the host, or inflated on the host and rebuilt on the device by one launch per scene.")
+    from . import openexr
+    openexr.add_inflate_argument(p, "--exr_decode device")
     return p
 
 
@@ -266,7 +268,7 @@ def main(args, log=print):
     for mode in (args.mode or list(j["modes"])):
         frame_set = FrameSet.from_json(args.json_filename, mode, log=log)
         stats = FrameStatistics(frame_set, j["modes"][mode].get("group_by_samples_per_pixel", False))
-        stats.compute(args.device, limit, max(1, min(args.threads, 8)), log, decode=args.exr_decode)
+        stats.compute(args.device, limit, max(1, min(args.threads, 8)), log, decode=args.exr_decode, inflate=args.exr_inflate)
         for path, spp, entries in stats.write(directory, mode):
             log("statistics: %s%s -- %d scene(s), %d window(s), %d skipped -> %s"
                 % (mode, "" if spp is None else " at %d samples per pixel" % spp, len(frame_set.scenes) - (len(stats.skipped) - len(frame_set.skipped)),

@@ -147,6 +147,8 @@ def parser():
                         "most 1; 1 replaces the score).  Default 0.5: a choice, not a measured optimum.")
     p.add_argument("--exr_decode", default="host", choices=["host", "device"],
                    help="--frames: where the EXR files are decoded: on the host, or inflated on the host and rebuilt on the device by one launch per scene.")
+    from . import openexr
+    openexr.add_inflate_argument(p, "--frames")
     p.add_argument("--frame_memory_gb", type=float, default=None,
                    help="The most device memory the frames may take (default: 80 %% of what is free when they are loaded).")
     p.add_argument("--seed", type=int, default=0, help="seed of the file / example shuffles and of the source index tuples (shared by all ranks)")
@@ -500,7 +502,7 @@ def main(args):
         threads = max(1, min(args.threads, 8))      # EXR decoders: a small fixed cap, whatever the host has
 
         def resident(mode, frames):
-            bank = FrameBank(arch, frames, spp, arch.device, limit, threads=threads, log=quiet, decode=args.exr_decode)
+            bank = FrameBank(arch, frames, spp, arch.device, limit, threads=threads, log=quiet, decode=args.exr_decode, inflate=args.exr_inflate)
             quiet("frames: %s -- %d scene(s), %d planes, %.3f GB on the device (%d spp, tiles of %d)"
                   % (mode, len(bank.scenes), bank.n_planes, bank.total_bytes / 1e9, bank.spp, bank.tile))
             return TileSampler(trainer.program, bank, usage)

@@ -907,6 +907,37 @@ typedef struct { float* dst; int H; int W; int C; int n_channels; int type[DD_EX
 int dd_exr_reconstruct(const dd_exr_chunk* chunks_host, const dd_exr_chunk* chunks, int n_chunks, const dd_exr_file* files_host,
                        const dd_exr_file* files, int n_files, void* staged, long staged_bytes, unsigned long long* counts, dd_stream stream);
 
+/* ---- The zlib streams of ZIP / ZIPS chunks inflated on the device (csrc/dd_exr_inflate.hip, decoder core csrc/dd_inflate_core.h).  Replaces
+ * the inflate inside the decode the reference leaves to OpenCV (OpenEXRDirectory.py:125-151: cv2.imdecode of the file's bytes) and the
+ * zlib.decompress calls of deepdenoiser_amd/openexr.py's host threads: the host only reads the files; ONE launch inflates every stream of a
+ * batch into the staged buffer, where dd_exr_reconstruct (same stream, no sync in between) expects each chunk's post-inflate bytes.
+ *   stream  : one zlib stream (RFC 1950 around RFC 1951: stored, fixed and dynamic blocks, any number of them) at src[src_offset ..
+ *             + src_bytes) that must expand to exactly dst_bytes bytes, written to staged + dst_offset (16-byte aligned; the stream owns the
+ *             bytes up to the next multiple of 16).  One wave per stream.
+ *   status  : DEVICE int[n_streams], one DD_INFLATE_* code per stream.  A stream whose status is DD_INFLATE_OK holds exactly the bytes
+ *             zlib's inflate gives for it (the Adler-32 is verified); the decoder may be stricter than zlib, never laxer.  A stream with
+ *             another status may leave anything inside its own dst_bytes (rounded up to 16) and nothing outside.
+ * The table is given twice: the HOST copy is validated here, the DEVICE copy is what the kernel reads -- and checks again
+ * (DD_INFLATE_RECORD: the record does not fit the buffers; nothing is read or written through it).
+ * Refused with a negative status and no launch: NULL pointers while n_streams > 0, n_streams < 0, src_bytes < 1, dst_bytes outside
+ * 1 .. 1 << 30, a source range leaving src_total, a dst_offset that is negative or not 16-byte aligned or whose dst_bytes rounded up to 16
+ * leave staged_bytes, a source that overlaps the staged buffer.  n_streams == 0 is a no-op that returns 0.  No host sync. */
+#define DD_INFLATE_OK 0
+#define DD_INFLATE_HEADER 1      /* method != 8, window bits > 15, (CMF * 256 + FLG) % 31 != 0, or FDICT set */
+#define DD_INFLATE_TRUNCATED 2   /* the input ends inside the header, a block, a symbol, extra bits or the Adler-32 */
+#define DD_INFLATE_BLOCK_TYPE 3  /* block type 3 */
+#define DD_INFLATE_STORED 4      /* LEN != ~NLEN */
+#define DD_INFLATE_LENGTHS 5     /* a defective dynamic header */
+#define DD_INFLATE_SYMBOL 6      /* literal/length symbol 286 / 287, distance symbol 30 / 31, or a bit pattern that is no code */
+#define DD_INFLATE_DISTANCE 7    /* a match reaching before the first output byte */
+#define DD_INFLATE_OVERRUN 8     /* output beyond dst_bytes */
+#define DD_INFLATE_SHORT 9       /* the final block ended with fewer bytes */
+#define DD_INFLATE_CHECK 10      /* Adler-32 mismatch */
+#define DD_INFLATE_RECORD 11     /* the device copy of the record does not fit the buffers */
+typedef struct { long long src_offset; long long dst_offset; int src_bytes; int dst_bytes; } dd_exr_stream;   /* 24 bytes */
+int dd_exr_inflate(const dd_exr_stream* streams_host, const dd_exr_stream* streams, int n_streams, const void* src, long src_total,
+                   void* staged, long staged_bytes, int* status, dd_stream stream);
+
 /* 3x3/s2 transpose conv (Tiramisu.py:62-64) = 3x3 SAME conv of the zero-stuffed input with the flipped kernel:
  * y[B,2H,2W,C] = 0 except y[2i+1,2j+1] = x[i,j]; and its adjoint dx[i,j] (+)= dy[2i+1,2j+1] * (mask>0). */
 int dd_zero_stuff(const void* x, int ldx, void* y, int ldy, int C, int B, int H, int W, int dtype, dd_stream stream);

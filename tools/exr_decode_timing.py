@@ -1,7 +1,7 @@
-"""Wall time of loading a frame bank from EXR files, decoded on the host or rebuilt on the device (openexr.DeviceDecoder,
-csrc/dd_exr_decode.hip), next to the HBM copy rate of the same box.
+"""Wall time of loading a frame bank from EXR files, decoded on the host, rebuilt on the device (openexr.DeviceDecoder,
+csrc/dd_exr_decode.hip) or inflated and rebuilt on the device (csrc/dd_exr_inflate.hip), next to the HBM copy rate of the same box.
 
-    python tools/exr_decode_timing.py [--decode host|device|both] [--threads 4] [--runs 3] [--height 1080] [--width 1920] [--out FILE]
+    python tools/exr_decode_timing.py [--decode host|device|device_inflate|both|all] [--threads 4] [--runs 3] [--height 1080] [--width 1920] [--out FILE]
 
 A synthetic tree is written into a temporary directory: two scenes x (1 source + 1 target rendering) x 9 three-channel passes, FLOAT, ZIP, a
 smooth image plus noise (the nine files of a rendering are written once and copied: what a decoder does does not depend on whose file it
@@ -9,7 +9,10 @@ is).  Timed: FrameBank.for_passes over the whole tree, `--runs` times per mode, 
 fp32 bytes of the planes).  Device mode also reports the device time of the dd_exr_reconstruct launches alone (HIP events around every
 launch; the kernel reads the staged bytes twice where a chunk is coded, rewrites them once and writes the planes -- `kernel_GB_per_s` counts
 staged bytes + plane bytes once, against bench.hbm_copy_rate of the same process) and the share of the wall time the loader spent waiting
-for the inflate threads."""
+for the inflate threads.  Mode device_inflate (decode on the device, inflate="device") adds the device time of the dd_exr_inflate launches
+alone (events), as compressed GB/s (the stream bytes read) and inflated GB/s (the bytes written), the bytes uploaded and the files redone on
+the host.  `both` is host + device, `all` (the default) the three modes in one process: the baseline of device_inflate is the `device` line
+of the same call."""
 import argparse
 import json
 import os
@@ -62,7 +65,7 @@ def write_tree(root, height, width, scenes=2):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--decode", default="both", choices=["host", "device", "both"])
+    ap.add_argument("--decode", default="all", choices=["host", "device", "device_inflate", "both", "all"])
     ap.add_argument("--threads", type=int, default=4)
     ap.add_argument("--runs", type=int, default=3)
     ap.add_argument("--height", type=int, default=1080)
@@ -84,12 +87,22 @@ def main():
         n_files = len(frame_set.scenes) * 2 * len(PASSES)
         file_bytes = sum(os.path.getsize(os.path.join(d, n)) for d, _, ns in os.walk(root) for n in ns if n.endswith(".exr"))
         copy_rate = bench.hbm_copy_rate(device)
-        for mode in (["host", "device"] if args.decode == "both" else [args.decode]):
-            seconds, kernel_ms, inflate, launches = [], [], [], 0
+        modes = {"both": ["host", "device"], "all": ["host", "device", "device_inflate"]}.get(args.decode, [args.decode])
+        stream_bytes = inflated_bytes = 0
+        if "device_inflate" in modes:                          # (what the inflate launches read and write: from the plans, outside the timing)
+            for d, _, ns in os.walk(root):
+                for n in ns:
+                    if n.endswith(".exr"):
+                        table = openexr.plan_file(os.path.join(d, n)).source_layout()[1]
+                        stream_bytes += int(table["src_bytes"].sum())
+                        inflated_bytes += int(table["dst_bytes"].sum())
+        for mode in modes:
+            seconds, kernel_ms, inflate, launches, inflate_ms, uploaded, fallbacks, inflate_launches = [], [], [], 0, [], 0, 0, 0
             for run in range(args.runs + 1):                   # (the first run warms the page cache, the allocator and the pinned ring)
                 torch.cuda.synchronize()
                 t0 = time.perf_counter()
-                bank = FrameBank.for_passes(frame_set, channels, channels, SPP, device=device, threads=args.threads, log=lambda m: None, decode=mode)
+                bank = FrameBank.for_passes(frame_set, channels, channels, SPP, device=device, threads=args.threads, log=lambda m: None,
+                                            decode="host" if mode == "host" else "device", inflate="device" if mode == "device_inflate" else "host")
                 torch.cuda.synchronize()
                 dt = time.perf_counter() - t0
                 created = [bank.decoder] if bank.decoder is not None else []
@@ -101,6 +114,10 @@ def main():
                         kernel_ms.append(sum(a.elapsed_time(b) for d in created for a, b in d.events))
                         inflate.append(sum(d.inflate_seconds for d in created) / dt)
                         launches = sum(d.launches for d in created)
+                        if mode == "device_inflate":
+                            inflate_ms.append(sum(a.elapsed_time(b) for d in created for a, b in d.inflate_events))
+                            uploaded, fallbacks = sum(d.uploaded_bytes for d in created), sum(d.host_fallbacks for d in created)
+                            inflate_launches = sum(d.inflate_launches for d in created)
                 del bank
             s = statistics.median(seconds)
             result = {"metric": "FrameBank from EXR files: wall seconds (median of %d)" % args.runs, "decode": mode, "threads": args.threads,
@@ -112,6 +129,12 @@ def main():
                 result.update({"launches": launches, "kernel_ms_all_launches": ms, "kernel_GB_per_s": 2 * plane_bytes / (ms * 1e-3) / 1e9,
                                "kernel_time_over_copy_time": copy_rate / (2 * plane_bytes / (ms * 1e-3) / 1e9),
                                "inflate_share_of_wall": statistics.median(inflate)})
+            if inflate_ms:
+                ms = statistics.median(inflate_ms)
+                result.update({"inflate_launches": inflate_launches, "inflate_ms_all_launches": ms, "inflate_ms_min": min(inflate_ms),
+                               "inflate_ms_max": max(inflate_ms), "compressed_GB": stream_bytes / 1e9, "inflated_GB": inflated_bytes / 1e9,
+                               "compressed_GB_per_s": stream_bytes / (ms * 1e-3) / 1e9, "inflated_GB_per_s": inflated_bytes / (ms * 1e-3) / 1e9,
+                               "uploaded_GB": uploaded / 1e9, "host_fallbacks": fallbacks})
             lines.append(json.dumps(result))
             print(lines[-1], flush=True)
     if args.out:
