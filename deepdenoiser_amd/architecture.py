@@ -121,6 +121,7 @@ class Architecture:
         self.number_of_output_channels = self.number_of_sources_per_target * tuple_size * self.member_channels
         self.feature_flag_names = sorted(t.name for t in self.feature_prediction_tuples)   # FeatureFlags.py:22
         self.params = ParamStore()
+        self.adam_step = 0                    # optimizer steps applied to the parameters (the t of Adam's bias correction; saved with a checkpoint)
         self._programs = {}
 
     def _prepare_feature_predictions(self, combined_json, handling_json, auxiliary_json):

@@ -92,6 +92,7 @@ class ParamStore:
     def __init__(self):
         self.params, self.by_name, self.total = [], {}, 0
         self.values = self.grads = self.m = self.v = None
+        self.raw_writes = 0     # launches that wrote the values through their raw pointer (state_key)
 
     def get(self, name, shape, fan_in=None, fan_out=None):
         if name in self.by_name:
@@ -125,7 +126,7 @@ class ParamStore:
         """Changes whenever the values may have: torch counts the in-place writes it performs on the arena and its views (load_list, checkpoint
         restore, tests), launches that write through the raw pointer (dd_adam_step) count themselves in `raw_writes`.  Lets an inference loop
         skip re-packing unchanged weights (prediction.Predictor)."""
-        return (self.values._version, getattr(self, "raw_writes", 0)) if self.values is not None else None
+        return (self.values._version, self.raw_writes) if self.values is not None else None
 
     def value(self, p):
         return self.values[p.offset:p.offset + p.size].view(p.shape)
@@ -244,9 +245,12 @@ class _Late:
 
 
 class Graph:
-    def __init__(self, device, dtype="f32", params=None):
+    def __init__(self, device, dtype="f32", params=None, training=True):
         assert dtype in _CODE
         self.lib = L.load()
+        # an inference graph drops what only a backward would read (the argmax plane of a max-pool, the zero-stuffed copy of a 3x3/s2
+        # transposed conv's input, the stacked images of a dense block)
+        self.training = training
         self.device, self.dtype, self.code = torch.device(device), dtype, _CODE[dtype]
         self.params = params if params is not None else ParamStore()
         self.pack_ops, self.fwd_ops, self.bwd_ops, self._tape = [], [], [], []
@@ -501,8 +505,9 @@ class Graph:
         return run
 
     # ------------------------------------------------------------------ differentiable ops
-    def conv(self, x, layer, relu=False, in_relu=False, res=None, out=None, split_at=None, no_backward=False):
+    def conv(self, x, layer, relu=False, in_relu=False, res=None, out=None, split_at=None, no_backward=False, no_forward=False):
         """tf.layers.conv2d(k x k, SAME) [+ residual] [+ ReLU]; `out` may be a channel view of a concat buffer.
+        no_forward: another launch of the caller writes y (the fused compose net); only the backward is recorded here.
         split_at: x is the concat [x[:, :split_at] | x[:, split_at:]] (the U-Net skip concat).  With more than 128 input channels in
         bf16 the 3x3 weights of a 32-channel block no longer fit LDS and the launch falls to 16-channel blocks (6 passes over the
         input for 192 -> 96); the forward then runs as conv(first part) followed by conv(second part) + that partial sum as residual:
@@ -514,6 +519,7 @@ class Graph:
         assert y.C == layer.cout
         ps = self.params
         flags = (L.OUT_RELU if relu else 0) | (L.IN_RELU if in_relu else 0)
+        forward = []
         do_split = (split_at is not None and self.dtype in ("bf16", "f16") and layer.k == 3 and res is None and layer.cin > 128
                     and 0 < split_at < layer.cin and split_at % 8 == 0 and max(split_at, layer.cin - split_at) <= 128
                     and os.environ.get("DD_CONV_SPLIT_CONCAT", "1") != "0")
@@ -522,10 +528,10 @@ class Graph:
             part = self.tensor(x.B, x.H, x.W, layer.cout, requires_grad=False)
             wa, taps, n_pad, ka_pad = layer.packed_k_range(0, split_at)
             wb, _, _, kb_pad = layer.packed_k_range(split_at, layer.cin - split_at)
-            self.fwd(self._defer(lambda: self._conv_call(xa, wa, taps, n_pad, ka_pad, ps.value_ptr(layer.bias), layer.cout, None, None, part,
-                                                         x.B, x.H, x.W, flags & L.IN_RELU, nk=(layer.cout, split_at)), "conv_igemm"))
-            self.fwd(self._defer(lambda: self._conv_call(xb, wb, taps, n_pad, kb_pad, None, 0, part, None, y,
-                                                         x.B, x.H, x.W, flags, nk=(layer.cout, layer.cin - split_at)), "conv_igemm"))
+            forward.append(self._defer(lambda: self._conv_call(xa, wa, taps, n_pad, ka_pad, ps.value_ptr(layer.bias), layer.cout, None, None, part,
+                                                                x.B, x.H, x.W, flags & L.IN_RELU, nk=(layer.cout, split_at)), "conv_igemm"))
+            forward.append(self._defer(lambda: self._conv_call(xb, wb, taps, n_pad, kb_pad, None, 0, part, None, y,
+                                                                x.B, x.H, x.W, flags, nk=(layer.cout, layer.cin - split_at)), "conv_igemm"))
         elif (self.dtype in ("bf16", "f16") and layer.k == 3 and res is None and (in_relu or layer.cin > 128) and layer.cout % 4 == 0 and layer.cout <= 256
               and x.ld % 8 == 0 and y.ld % 4 == 0 and x.ch0 % 8 == 0 and y.ch0 % 4 == 0 and os.environ.get("DD_CONV_KS", "1") != "0"
               # thin layers over a short reduction (<= 32 new channels from <= 144: the 256 x 256 level of the light Tiramisu) keep their whole weight
@@ -535,11 +541,14 @@ class Graph:
             # Tiramisu's dense-block convs (pre-activation, reduction over the growing concat: K = 9 x up to 1 088 channels, 16 ... 128 new
             # channels): both operands streamed per 64-channel K-slice (csrc/dd_conv_ks.hip); the LDS-weight kernel can keep none of it resident
             wp, taps, n_pad, k_pad = layer.packed("fwd")
-            self.fwd(self._defer(lambda: self._conv_ks_call("ks_fwd", x, y, layer.cout, layer.cin, wp, n_pad, k_pad, flags, bias=layer), "conv_igemm"))
+            forward.append(self._defer(lambda: self._conv_ks_call("ks_fwd", x, y, layer.cout, layer.cin, wp, n_pad, k_pad, flags, bias=layer), "conv_igemm"))
         else:
             wp, taps, n_pad, k_pad = layer.packed("fwd")
-            self.fwd(self._defer(lambda: self._conv_call(x, wp, taps, n_pad, k_pad, ps.value_ptr(layer.bias), layer.cout, res, None, y,
-                                                         x.B, x.H, x.W, flags, nk=(layer.cout, layer.cin)), "conv_igemm"))
+            forward.append(self._defer(lambda: self._conv_call(x, wp, taps, n_pad, k_pad, ps.value_ptr(layer.bias), layer.cout, res, None, y,
+                                                                x.B, x.H, x.W, flags, nk=(layer.cout, layer.cin)), "conv_igemm"))
+        if not no_forward:
+            for op in forward:
+                self.fwd(op)
 
         def backward():
             if not y.grad_written:
@@ -616,7 +625,7 @@ class Graph:
             cj = c0 + j * f
             assert lay.cin == cj and lay.cout == f and lay.k == 3
             self.conv(buf.view(0, cj), lay, relu=False, in_relu=True, out=buf.view(cj, f, relu=False), no_backward=gather)
-        if not gather or not bool(getattr(self, "training", True)):      # the stacked images below only feed the backward
+        if not gather or not self.training:      # the stacked images below only feed the backward
             return c0 + n * f
         ps = self.params
 
@@ -752,9 +761,9 @@ class Graph:
         # ... and so does the BACKWARD (round 3): with the output gradient rearranged by output parity (dd_space_to_depth2) the data gradient is a
         # 2 x 2-tap conv on the input grid (dd_conv3x3_ks mode 6) and the filter gradient one GEMM over nine shifted channel windows
         # (dd_convt3_wgrad): no zero-stuffed tensor, no 4x-redundant MACs.  DD_CONVT3_S2D_BWD=0: differentiate the zero-stuffed form instead.
-        s2d_bwd = (parity and bool(getattr(self, "training", True)) and x.ld % 8 == 0 and x.ch0 % 8 == 0 and layer.cin % 4 == 0
+        s2d_bwd = (parity and self.training and x.ld % 8 == 0 and x.ch0 % 8 == 0 and layer.cin % 4 == 0
                    and os.environ.get("DD_CONVT3_S2D_BWD", "1") != "0")      # (the s2d image only feeds the backward)
-        need_z = (not parity) or (bool(getattr(self, "training", True)) and not s2d_bwd)
+        need_z = (not parity) or (self.training and not s2d_bwd)
         z = self.tensor(x.B, 2 * x.H, 2 * x.W, x.C, requires_grad=x.requires_grad) if need_z else None
         if s2d_bwd:
             # data-gradient operand [9][cin][4 cp]: image tap (1 + (a == 2), 1 + (b == 2)), column block plane(a, b) = K[a][b][:, :] transposed
@@ -841,7 +850,7 @@ class Graph:
         y = out if out is not None else self.tensor(x.B, OH, OW, x.C, requires_grad=x.requires_grad)
         assert (y.H, y.W, y.C) == (OH, OW, x.C)
         # the argmax plane only feeds the backward: inference graphs do not store it
-        idx = torch.zeros((x.B, OH, OW, x.Cp), dtype=torch.uint8, device=self.device) if bool(getattr(self, "training", True)) else None
+        idx = torch.zeros((x.B, OH, OW, x.Cp), dtype=torch.uint8, device=self.device) if self.training else None
         lib, code = self.lib, self.code
 
         def run(stream):
@@ -874,7 +883,8 @@ class Graph:
     def finalize(self, seed=2):
         """Allocates the parameters, then binds every queued launch, in program order.  From here on the three lists hold bound launches only:
         calling one issues library calls and nothing else, and each carries its record (`info`) -- written to conv_records / wgrad_records /
-        bwd_records / convt_records by the bind, so a launch that was taken out of the lists before leaves no record."""
+        bwd_records / convt_records by the bind.  The builders queue only what will run; the members of a merged launch (_merge_weights_only)
+        are the one exception, and they never bind: their one maker writes the records."""
         self.params.finalize(self.device, seed)
         for ops in (self.pack_ops, self.fwd_ops, self.bwd_ops):
             ops[:] = [op.bind() if isinstance(op, _Late) else op for op in ops]

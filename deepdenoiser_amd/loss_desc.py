@@ -2,7 +2,11 @@
 
 Host only: ctypes structures are filled and buffers allocated, nothing is launched.  The loss build (program.py) and the tracked metrics,
 histograms and image summaries (tracking.py) all name the sources of a scale through fill_sources; which sources exist is decided by
-metrics.combined_levels / metrics.combined_triples, which pass defines a mask by metrics.mask_pass."""
+metrics.combined_levels / metrics.combined_triples, which pass defines a mask by metrics.mask_pass.  loss_plan decides what the loss of a
+training program evaluates before the program records anything."""
+import os
+import types
+
 import torch
 
 from . import _lib as L
@@ -11,6 +15,60 @@ from .render_passes import RenderPasses
 
 LOSS_KIND = {"DIFFERENCE": 1, "ABSOLUTE": 2, "SMOOTH_ABSOLUTE": 3, "SQUARED": 4, "SMAPE": 5}
 EPSILON = 1e-2      # the epsilon of the SMAPE form (LossDifference.py:18-34)
+
+
+def check_ms_ssim(head, dim, q_feat):
+    """Build-time rules of the ms_ssim term (BaseFeatureTraining.ms_ssim, Training.py:178-204) on tiles of dim = (h, w)."""
+    h, w = dim
+    if h % 4 or w % 4 or min(h, w) < 44:
+        raise ValueError("the ms_ssim loss term needs tiles whose height and width are multiples of 4 and at least 44 (got %d x %d): "
+                         "tf.image.ssim_multiscale refuses a level smaller than its 11 x 11 filter (3 levels: side / 4 >= 11), and "
+                         "levels of odd size would need its symmetric pad before the 2x2 pool, which is not built" % (h, w))
+    if q_feat > 0:
+        for f in head:
+            if f.load_data and f.number_of_channels != 3:
+                raise ValueError("a features-level ms_ssim weight cannot be used with the loaded 1-channel target pass '%s': the reference "
+                                 "transposes such a tensor into an image 1 pixel high (Training.py:187-190) and cannot build either" % f.name)
+
+
+def loss_plan(arch, head, training_json, dims):
+    """What the loss of a training program evaluates, decided before anything is recorded (Training.model_fn, Training.py:607-660): the weights
+    of the three levels, which sources exist, how many scales carry a loss, and whether dd_loss_head runs the inverse standardization of those
+    scales itself (fuse_invert).  dims: (h, w) of every scale.  Raises what the reference raises for settings it cannot build."""
+    tj = training_json
+
+    def w3(j):      # (mean, variation, ms_ssim) weights of one level (BaseFeatureTraining.loss, Training.py:210-243)
+        return float(j["mean"]), float(j["variation"]), float(j["ms_ssim"])
+
+    def wm(j):      # masked-mean weight of one level (Training.py:131-137, 233-241)
+        if j and j["ms_ssim"] > 0:
+            raise NotImplementedError("the masked ms_ssim loss term cannot run: the reference raises 'Not implemented' there too "
+                                      "(BaseFeatureTraining.masked_ms_ssim, Training.py:206-207)")
+        if j and j["variation"] > 0:
+            raise NotImplementedError("the masked variation loss term is out of scope (weight 0 in TrainingExample.json)")
+        return float(j["mean"]) if j else 0.0
+    fs, cf, ci = tj["features_training_settings"], tj["combined_features_training_settings"], tj["combined_image_training_settings"]
+    p = types.SimpleNamespace()
+    p.masked_features, p.masked_combined = wm(fs.get("loss_weights_masked")), wm(cf.get("loss_weights_masked"))
+    p.features, p.combined, p.image = w3(fs["loss_weights"]), w3(cf["loss_weights"]), w3(ci["loss_weights"])
+    p.use_image, p.use_comb = M.combined_levels(tj)      # Training.py:1063-1093
+    p.triples = M.combined_triples(arch) if p.use_comb else []
+    p.loss_scales = len(dims) if tj["use_multiscale_loss"] else 1
+    p.norm = 1.0 / sum(1.0 / 4.0 ** s for s in range(p.loss_scales))
+    # (decided by the sources that exist, not by the weights alone: a combined-features weight on a network without a complete triple
+    # evaluates nothing and must not cost the fused launch)
+    p.ms_ssim = (p.features[2] > 0 and any(f.load_data for f in head)) or (p.combined[2] > 0 and len(p.triples) > 0) or p.image[2] > 0
+    if p.ms_ssim:
+        check_ms_ssim(head, dims[0], p.features[2])
+    # A loss without variation terms (every term a function of one pixel) behind an inverse standardization that feeds nothing else: the
+    # inversion and its gradient run inside dd_loss_head (one launch per scale instead of three; DD_FUSE_LOSS_INVERT=0 keeps them apart)
+    # (an ms_ssim term rules the fusion out like a variation term does: the fused launch leaves dL/d(standardized value) in dpred, and
+    # dd_loss_msssim_bwd adds a gradient with respect to the inverted value)
+    p.fuse_invert = (arch.invert_standardization_after_multiscale_predictions and p.features[1] == 0 and p.combined[1] == 0 and p.image[1] == 0
+                     and not p.ms_ssim and os.environ.get("DD_FUSE_LOSS_INVERT", "1") != "0")
+    if p.masked_features > 0 and any(f.load_data and f.name == "Alpha" for f in head):
+        raise Exception("Masking is not supported for the alpha pass, because it does not seem to make sense.")   # Training.py:103-113
+    return p
 
 
 def block_ptr(t, image_offset):

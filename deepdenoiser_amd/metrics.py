@@ -109,7 +109,7 @@ def metric_plan(arch, training_json, out=print, histograms=False):
     loaded pass the reference would index an empty mask list and fail; such a pass is LEFT OUT here (Alpha is refused like the reference).
 
     Raises, naming the key, when a flag that cannot be served is true: statistics_masked.track_variation, statistics_masked.track_ms_ssim,
-    any masked tracking with an Alpha pass, track_ms_ssim of the features level with a loaded 1-channel pass (Program._check_ms_ssim adds
+    any masked tracking with an Alpha pass, track_ms_ssim of the features level with a loaded 1-channel pass (loss_desc.check_ms_ssim adds
     the tile-size rule when the launches are built).  A *_histogram flag is not this plan's business (histogram_plan): a caller that does
     not write histograms (histograms=False) has that said once through `out`."""
     tj = training_json

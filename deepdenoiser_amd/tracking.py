@@ -51,7 +51,7 @@ class Metrics:
             self.launches.append(run)
         if ms_sources:      # BaseFeatureTraining.ms_ssim, Training.py:178-204: always predicted[0] / target[0]
             h, w = prog.dims[0]
-            prog._check_ms_ssim((h, w), 1.0 if any(src[0] == "feature" for src in ms_sources) else 0.0)
+            LD.check_ms_ssim(prog.head, (h, w), 1.0 if any(src[0] == "feature" for src in ms_sources) else 0.0)
             m, n_sources = LD.ms_ssim_desc(LD.sources_desc(prog, 0, triples, use_image),      # (a positive weight selects the source)
                                            [1.0 if ("feature", f.name) in ms_sources else 0.0 for f in prog.head],
                                            [1.0 if ("combined", c) in ms_sources else 0.0 for c, _ in triples],

@@ -1,7 +1,7 @@
 """Every launch is bound when Program(...) returns (engine.Graph.finalize): no list entry is an unbound maker, every launch of an MFMA family
-carries its record as `info`, and a family's records say what its listed launches say -- a launch that was taken out of the lists before
-finalize() (the layer-wise compose net behind the fused launch, the inversion the loss head takes over, the members of a merged launch) leaves
-no record.  Built on the CPU device from the cross-compiled library; nothing is launched."""
+carries its record as `info`, and a family's records say what its listed launches say -- the builders queue only what will run (a fused
+compose net or a loss head that inverts the standardization itself records no layer-wise launch), and the members of a merged launch never
+bind, so they leave no record.  Built on the CPU device from the cross-compiled library; nothing is launched."""
 import pytest
 
 from deepdenoiser_amd import configs, engine

@@ -120,9 +120,9 @@ def _check(arch, tj, prog, B):
         sf = norm / 4.0 ** s
         block = B * h * w * 3 * 4
         P = prog.predictions[s]
-        rec = prog._invert_records.get(id(P)) if fused else None
+        rec = prog.loss_inverts.get(s)      # (standardized prediction, groups) of an inversion the loss head runs itself
         assert (rec is not None) == (fused and any(f.load_data for f in head)), "the fused inversion is taken exactly when nothing rules it out"
-        grad = (rec["x"] if rec is not None else P).gstate["buf"]
+        grad = (rec[0] if rec is not None else P).gstate["buf"]
         assert d.n_features == len(head) and d.kind == {"SMAPE": 5, "SMOOTH_ABSOLUTE": 3}[tj["loss_difference"]] and d.epsilon == _f32(1e-2)
         masked = False
         for i, f in enumerate(head):
@@ -130,7 +130,7 @@ def _check(arch, tj, prog, B):
             assert d.pred_ld[i] == 3
             if f.load_data:
                 assert d.pred[i] == P.buf.data_ptr() + i * block and d.dpred[i] == grad.data_ptr() + i * block, f.name
-                assert d.pred_std[i] == (rec["x"].buf.data_ptr() + i * block if rec is not None else None), f.name
+                assert d.pred_std[i] == (rec[0].buf.data_ptr() + i * block if rec is not None else None), f.name
                 assert d.pred_inv[i] == (d.pred[i] if rec is not None else None), f.name
                 assert (d.weight[i], d.var_weight[i]) == (_f32(weights[0]["mean"] * sf), _f32(weights[0]["variation"] * sf)), f.name
                 cp = _colour_pass(f.name) if m_feat > 0 else None
