@@ -52,6 +52,7 @@ SYMBOLS = (
     "dd_nonfinite_scan", "dd_nonfinite_repair", "dd_frame_quality_scratch_bytes", "dd_frame_quality", "dd_stitch_blend",
     "dd_grad_norms", "dd_adam_step_clipped", "dd_adam_step_scaled_clipped", "dd_sample_tiles",
     "dd_tile_statistics", "dd_importance_cells", "dd_importance_update", "dd_exr_reconstruct", "dd_exr_inflate",
+    "dd_exr_pack", "dd_exr_deflate_workspace", "dd_exr_deflate",
 )
 
 
@@ -285,6 +286,20 @@ class ExrStream(C.Structure):          # dd_exr_stream: one zlib stream of dd_ex
     _fields_ = [("src_offset", C.c_longlong), ("dst_offset", C.c_longlong), ("src_bytes", C.c_int), ("dst_bytes", C.c_int)]
 
 
+class ExrSource(C.Structure):          # dd_exr_source: the fp32 plane a file is packed from and, per file channel, its pixel type and plane channel
+    _fields_ = [("src", C.c_void_p), ("H", C.c_int), ("W", C.c_int), ("C", C.c_int), ("n_channels", C.c_int),
+                ("type", C.c_int * EXR_MAX_CHANNELS), ("src_channel", C.c_int * EXR_MAX_CHANNELS)]
+
+
+class ExrDeflateStream(C.Structure):   # dd_exr_deflate_stream: one packed chunk of dd_exr_deflate and the slot of its zlib stream (24 bytes)
+    _fields_ = [("src_offset", C.c_longlong), ("dst_offset", C.c_longlong), ("src_bytes", C.c_int), ("dst_capacity", C.c_int)]
+
+
+# DD_DEFLATE_*: the per-stream status codes of dd_exr_deflate
+DEFLATE_OK, DEFLATE_RAW, DEFLATE_RECORD = range(3)
+DEFLATE_STATUS_NAMES = ("OK", "RAW", "RECORD")
+DEFLATE_BLOCK_TOKENS = 16384     # DD_DEFLATE_BLOCK_TOKENS (csrc/dd_deflate_core.h): 32-bit tokens per stream in the workspace
+
 # DD_INFLATE_*: the per-stream status codes of dd_exr_inflate
 (INFLATE_OK, INFLATE_HEADER, INFLATE_TRUNCATED, INFLATE_BLOCK_TYPE, INFLATE_STORED, INFLATE_LENGTHS, INFLATE_SYMBOL, INFLATE_DISTANCE,
  INFLATE_OVERRUN, INFLATE_SHORT, INFLATE_CHECK, INFLATE_RECORD) = range(12)
@@ -493,6 +508,10 @@ def load():
     lib.dd_importance_update.argtypes = [C.POINTER(ImportanceUpdateDesc), vp, i, i, i, i, i, vp, vp, vp]
     lib.dd_exr_reconstruct.argtypes = [vp, vp, i, vp, vp, i, vp, l, vp, vp]
     lib.dd_exr_inflate.argtypes = [vp, vp, i, vp, l, vp, l, vp, vp]
+    lib.dd_exr_pack.argtypes = [vp, vp, i, vp, vp, i, vp, l, vp]
+    lib.dd_exr_deflate_workspace.argtypes = [i]
+    lib.dd_exr_deflate_workspace.restype = l
+    lib.dd_exr_deflate.argtypes = [vp, vp, i, vp, l, vp, l, vp, l, vp, vp, vp]
     _lib = lib
     return lib
 

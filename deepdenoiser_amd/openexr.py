@@ -754,6 +754,302 @@ class DeviceDecoder:
         return results
 
 
+# ---------------------------------------------------------------------------------------------------- encode on the device
+# The inverse of the above.  The host keeps the header, the offset table and the file; one dd_exr_pack launch (csrc/dd_exr_encode.hip) turns the
+# fp32 planes of a whole batch of files into chunk bytes (samples, row and channel order, byte split, predictor), one dd_exr_deflate launch
+# (csrc/dd_exr_deflate.hip) turns every chunk into a zlib stream.  plan_write and assemble need no device.
+SOURCE_DTYPE = np.dtype([("src", "<u8"), ("H", "<i4"), ("W", "<i4"), ("C", "<i4"), ("n_channels", "<i4"), ("type", "<i4", (8,)),
+                         ("src_channel", "<i4", (8,))])                                                                  # dd_exr_source
+DEFLATE_STREAM_DTYPE = np.dtype([("src_offset", "<i8"), ("dst_offset", "<i8"), ("src_bytes", "<i4"), ("dst_capacity", "<i4")])      # dd_exr_deflate_stream
+DEFLATE_OK, DEFLATE_RAW, DEFLATE_RECORD = 0, 1, 2               # DD_DEFLATE_*
+HALF, FLOAT = 1, 2                                              # pixel types of a written channel
+_TYPE_NAMES = {"half": HALF, "float": FLOAT, HALF: HALF, FLOAT: FLOAT}
+
+
+def _pixel_type(value):
+    if value not in _TYPE_NAMES:
+        raise ValueError("pixel type %r (float or half)" % (value,))
+    return _TYPE_NAMES[value]
+
+
+class WritePlan:
+    """What plan_write lays out for one file.  header: the bytes in front of the offset table; names / types / src_channels: the file's
+    channels in name order; chunks: CHUNK_DTYPE records (`file` left 0) whose offset is the chunk's slot, relative to the file's slot bytes;
+    raw_bytes: per chunk its n; slot_bytes: how many slot bytes the file has.  A slot is 16-byte aligned and _align(n) long: it takes the
+    chunk's packed bytes in the pack buffer, and in the output buffer its zlib stream (at most dst_capacity = n - 1 bytes) or, stored raw,
+    its n plain bytes.  coded: whether the chunks are predicted and deflated (ZIP, ZIPS) or plain (NONE)."""
+
+    def __init__(self, path, height, width, names, types, src_channels, compression, header, chunks, raw_bytes, slot_bytes):
+        self.path, self.height, self.width, self.names, self.types, self.src_channels = path, height, width, names, types, src_channels
+        self.compression, self.header, self.chunks, self.raw_bytes, self.slot_bytes = compression, header, chunks, raw_bytes, slot_bytes
+        self.coded = compression in (ZIP_COMPRESSION, ZIPS_COMPRESSION)
+
+    def streams(self):
+        """DEFLATE_STREAM_DTYPE records of the file's chunks, offsets relative to the file's slot bytes"""
+        table = np.zeros(len(self.chunks), dtype=DEFLATE_STREAM_DTYPE)
+        table["src_offset"] = table["dst_offset"] = self.chunks["offset"]
+        table["src_bytes"] = self.raw_bytes
+        table["dst_capacity"] = np.asarray(self.raw_bytes) - 1
+        return table
+
+
+def plan_write(path, height, width, names, types, compression=ZIP_COMPRESSION, src_channels=None):
+    """The host half of a device encode, without a device: channel `names` (any order) with their pixel `types` (HALF / FLOAT, or "half" /
+    "float") and the plane channel each is read from (default: its index in `names`) -> WritePlan.  The header is byte-identical to the
+    one write_exr writes for the same channels."""
+    if compression not in (NO_COMPRESSION, ZIPS_COMPRESSION, ZIP_COMPRESSION):
+        raise ExrError("the device writes NONE, ZIPS and ZIP, not %s" % _CODEC_NAMES.get(compression, compression))
+    if height < 1 or width < 1:
+        raise ExrError("%s: empty image (%d x %d)" % (path, width, height))
+    if not 1 <= len(names) <= MAX_FILE_CHANNELS or len(set(names)) != len(names):
+        raise ExrError("%s: %d channels (1 .. %d distinct names)" % (path, len(names), MAX_FILE_CHANNELS))
+    src_channels = list(range(len(names))) if src_channels is None else list(src_channels)
+    order = sorted(range(len(names)), key=lambda k: names[k])
+    names, types, src_channels = [names[k] for k in order], [_pixel_type(types[k]) for k in order], [int(src_channels[k]) for k in order]
+    chlist = b"".join(n.encode("latin-1") + b"\0" + struct.pack("<iB3xii", t, 0, 1, 1) for n, t in zip(names, types)) + b"\0"
+    box = struct.pack("<4i", 0, 0, width - 1, height - 1)
+    header = struct.pack("<ii", MAGIC, 2)
+    header += _attr("channels", "chlist", chlist) + _attr("compression", "compression", bytes([compression]))
+    header += _attr("dataWindow", "box2i", box) + _attr("displayWindow", "box2i", box) + _attr("lineOrder", "lineOrder", b"\0")
+    header += _attr("pixelAspectRatio", "float", struct.pack("<f", 1.0)) + _attr("screenWindowCenter", "v2f", struct.pack("<2f", 0, 0))
+    header += _attr("screenWindowWidth", "float", struct.pack("<f", 1.0)) + b"\0"
+    lines = _LINES[compression]
+    row_bytes = sum(width * _PIXEL[t].itemsize for t in types)
+    n_chunks = (height + lines - 1) // lines
+    chunks, raw_bytes, at = np.zeros(n_chunks, dtype=CHUNK_DTYPE), [], 0
+    coded = int(compression != NO_COMPRESSION)
+    for k in range(n_chunks):
+        row0 = k * lines
+        rows = min(lines, height - row0)
+        if rows * row_bytes > MAX_STREAM_BYTES:
+            raise ExrError("%s: a chunk of %d bytes; the device takes at most %d" % (path, rows * row_bytes, MAX_STREAM_BYTES))
+        chunks[k] = (at, 0, row0, rows, coded)
+        raw_bytes.append(rows * row_bytes)
+        at += _align(rows * row_bytes)
+    return WritePlan(path, height, width, names, types, src_channels, compression, header, chunks, raw_bytes, at)
+
+
+def assemble(plan, statuses, sizes, slots):
+    """The file's bytes: header, offset table, then int32 y | int32 size | data per chunk.  statuses / sizes: what dd_exr_deflate gave for the
+    file's chunks (ignored for NONE); slots: the file's slot bytes -- of a chunk whose status is OK its zlib stream, of one that is RAW
+    (and of every chunk of a NONE file) its plain bytes."""
+    slots = memoryview(slots)
+    parts = []
+    for k, (record, n) in enumerate(zip(plan.chunks, plan.raw_bytes)):
+        at = int(record["offset"])
+        size = n
+        if plan.coded:
+            status = int(statuses[k])
+            if status == DEFLATE_OK:
+                size = int(sizes[k])
+                if not 1 <= size < n:
+                    raise ExrError("%s: chunk %d: a stream of %d bytes for %d" % (plan.path, k, size, n))
+            elif status != DEFLATE_RAW:
+                raise ExrError("%s: chunk %d: deflate status %d" % (plan.path, k, status))
+        parts.append((int(record["row0"]), slots[at:at + size]))
+    pos = len(plan.header) + 8 * len(parts)
+    table = []
+    for _, data in parts:
+        table.append(pos)
+        pos += 8 + len(data)
+    out = bytearray(plan.header) + struct.pack("<%dQ" % len(table), *table)
+    for y, data in parts:
+        out += struct.pack("<ii", y, len(data))
+        out += data
+    return bytes(out)
+
+
+def _image_channels(shape):
+    """write_image's channel naming: [H,W,3] is R, G, B; [H,W] is Y -> (names, plane channels)"""
+    if len(shape) == 2:
+        return ["Y"], 1
+    if len(shape) != 3 or shape[2] != 3:
+        raise ExrError("the writer takes [H,W,3] or [H,W], got %s" % (tuple(shape),))
+    return ["R", "G", "B"], 3
+
+
+class DeviceEncoder:
+    """fp32 device planes to EXR files, all files of a call in one batch: one dd_exr_pack launch, one dd_exr_deflate launch, one
+    synchronisation to read statuses and sizes, a second dd_exr_pack launch (coded = 0) for exactly the chunks that did not shrink, written
+    straight into their slots, one download into a pinned buffer, and the files written on `threads` threads (at most 16).  The planes read
+    back bit-identical through read_image (FLOAT) or as astype(float16) (HALF).  ZIP, ZIPS and NONE run on the device; RLE goes through the
+    host writer.  The buffers grow to the largest batch seen, are reused across calls and given back by release()."""
+    time_launches = False                                       # measurements: keep (start, end) events of the launches in pack_events / deflate_events
+
+    def __init__(self, device, compression=ZIP_COMPRESSION, threads=4):
+        import torch
+        self.device = torch.device(device)
+        if compression not in _LINES:
+            raise ExrError("cannot write compression %s" % _CODEC_NAMES.get(compression, compression))
+        if self.device.type != "cuda":
+            raise ValueError("EXR files are encoded on a GPU: %s is none" % (self.device,))
+        if self.device.index is None:
+            self.device = torch.device("cuda", torch.cuda.current_device())
+        self.compression = compression
+        self.threads = max(1, min(int(threads), 16))
+        self._packed = self._out = self._workspace = self._tables = self._pinned = self._pinned_tables = None
+        self.pack_launches = self.deflate_launches = self.raw_chunks = self.downloaded_bytes = 0
+        self.host_seconds = 0.0                                 # wall time encode() spent assembling and writing the files
+        self.pack_events, self.deflate_events = [], []
+
+    def release(self):
+        """Give the device and the pinned buffers back (the counters stay)."""
+        import torch
+        torch.cuda.synchronize(self.device)
+        self._packed = self._out = self._workspace = self._tables = self._pinned = self._pinned_tables = None
+
+    def _grow(self, name, nbytes, pinned=False):
+        import torch
+        have = getattr(self, name)
+        if have is None or have.numel() < nbytes:
+            have = torch.empty(nbytes, dtype=torch.uint8, pin_memory=True) if pinned else torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+            setattr(self, name, have)
+        return have
+
+    def _timed(self, events, stream, launch):
+        import torch
+        if not self.time_launches:
+            return launch()
+        events.append((torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)))
+        events[-1][0].record(stream)
+        launch()
+        events[-1][1].record(stream)
+
+    def encode(self, requests):
+        """requests: [(path, fp32 tensor [H,W,3] (written as R, G, B) or [H,W] (as Y) on the device, "float" / "half"), ...] -> the paths."""
+        import concurrent.futures
+        import time
+
+        import torch
+
+        from . import _lib as L
+        requests = [(path, image, _pixel_type(kind)) for path, image, kind in requests]
+        if self.compression == RLE_COMPRESSION:                 # the run-length coder stays on the host
+            for path, image, kind in requests:
+                arr = image.detach().cpu().numpy().astype(np.float16 if kind == HALF else np.float32)
+                names, _ = _image_channels(arr.shape)
+                write_exr(path, {"Y": arr} if len(names) == 1 else {c: np.ascontiguousarray(arr[..., i]) for i, c in enumerate(names)}, RLE_COMPRESSION)
+            return [path for path, _, _ in requests]
+        if not requests:
+            return []
+        lib = L.load()
+        planes, plans = [], []
+        for path, image, kind in requests:
+            if not torch.is_tensor(image) or image.device != self.device or image.dtype != torch.float32:
+                raise ValueError("%s: the encoder takes fp32 tensors on %s" % (path, self.device))
+            names, channels = _image_channels(image.shape)
+            planes.append(image.detach().contiguous())
+            plans.append(plan_write(path, image.shape[0], image.shape[1], names, [kind] * len(names), self.compression))
+        # ---- layout: the slots of all files | per file a base; the tables: chunks | sources | streams | chunks of the second pack launch
+        bases, at = [], 0
+        for p in plans:
+            bases.append(at)
+            at += p.slot_bytes
+        total = max(at, _STAGE_ALIGN)
+        n_chunks = sum(len(p.chunks) for p in plans)
+        coded = plans[0].coded
+        sources_at = _align(n_chunks * CHUNK_DTYPE.itemsize)
+        streams_at = _align(sources_at + len(plans) * SOURCE_DTYPE.itemsize)
+        redo_at = _align(streams_at + n_chunks * DEFLATE_STREAM_DTYPE.itemsize)
+        tables_bytes = redo_at + n_chunks * CHUNK_DTYPE.itemsize
+        host = self._grow("_pinned_tables", tables_bytes, pinned=True).numpy()
+        chunk_table = host[:n_chunks * CHUNK_DTYPE.itemsize].view(CHUNK_DTYPE)
+        source_table = host[sources_at:sources_at + len(plans) * SOURCE_DTYPE.itemsize].view(SOURCE_DTYPE)
+        stream_table = host[streams_at:streams_at + n_chunks * DEFLATE_STREAM_DTYPE.itemsize].view(DEFLATE_STREAM_DTYPE)
+        source_table[:] = np.zeros((), dtype=SOURCE_DTYPE)
+        n = 0
+        for slot, (p, plane, base) in enumerate(zip(plans, planes, bases)):
+            row = source_table[slot]
+            row["src"], row["H"], row["W"], row["C"], row["n_channels"] = plane.data_ptr(), p.height, p.width, 1 if plane.dim() == 2 else plane.shape[2], len(p.names)
+            row["type"][:len(p.types)] = p.types
+            row["src_channel"][:len(p.types)] = p.src_channels
+            part = chunk_table[n:n + len(p.chunks)]
+            part[:] = p.chunks
+            part["offset"] += base
+            part["file"] = slot
+            part = stream_table[n:n + len(p.chunks)]
+            part[:] = p.streams()
+            part["src_offset"] += base
+            part["dst_offset"] += base
+            n += len(p.chunks)
+        with torch.cuda.device(self.device):
+            stream = torch.cuda.current_stream(self.device)
+            out = self._grow("_out", total)
+            tables = self._grow("_tables", tables_bytes)
+            tables[:tables_bytes].copy_(self._pinned_tables[:tables_bytes], non_blocking=True)
+            statuses = sizes = None
+            if coded:
+                packed = self._grow("_packed", total)
+                workspace_bytes = int(lib.dd_exr_deflate_workspace(n_chunks))
+                workspace = self._grow("_workspace", workspace_bytes)
+                self._timed(self.pack_events, stream, lambda: L.check(lib.dd_exr_pack(
+                    host.ctypes.data, tables.data_ptr(), n_chunks, host[sources_at:].ctypes.data, tables.data_ptr() + sources_at, len(plans),
+                    packed.data_ptr(), total, stream.cuda_stream)))
+                self.pack_launches += 1
+                both = torch.empty(2 * n_chunks, dtype=torch.int32, device=self.device)
+                self._timed(self.deflate_events, stream, lambda: L.check(lib.dd_exr_deflate(
+                    host[streams_at:].ctypes.data, tables.data_ptr() + streams_at, n_chunks, packed.data_ptr(), total, out.data_ptr(), total,
+                    workspace.data_ptr(), workspace_bytes, both.data_ptr(), both.data_ptr() + 4 * n_chunks, stream.cuda_stream)))
+                self.deflate_launches += 1
+                both = both.cpu().numpy()                           # the one synchronisation
+                statuses, sizes = both[:n_chunks], both[n_chunks:]
+                raw = np.flatnonzero(statuses == DEFLATE_RAW)
+                if len(raw):
+                    redo = host[redo_at:redo_at + len(raw) * CHUNK_DTYPE.itemsize].view(CHUNK_DTYPE)
+                    redo[:] = chunk_table[raw]
+                    redo["coded"] = 0
+                    nbytes = len(raw) * CHUNK_DTYPE.itemsize
+                    tables[redo_at:redo_at + nbytes].copy_(self._pinned_tables[redo_at:redo_at + nbytes], non_blocking=True)
+                    self._timed(self.pack_events, stream, lambda: L.check(lib.dd_exr_pack(
+                        host[redo_at:].ctypes.data, tables.data_ptr() + redo_at, len(raw), host[sources_at:].ctypes.data, tables.data_ptr() + sources_at,
+                        len(plans), out.data_ptr(), total, stream.cuda_stream)))
+                    self.pack_launches += 1
+                    self.raw_chunks += len(raw)
+            else:
+                self._timed(self.pack_events, stream, lambda: L.check(lib.dd_exr_pack(
+                    host.ctypes.data, tables.data_ptr(), n_chunks, host[sources_at:].ctypes.data, tables.data_ptr() + sources_at, len(plans),
+                    out.data_ptr(), total, stream.cuda_stream)))
+                self.pack_launches += 1
+            pinned = self._grow("_pinned", total, pinned=True)
+            pinned[:total].copy_(out[:total], non_blocking=True)
+            stream.synchronize()
+            self.downloaded_bytes += total
+        t0 = time.perf_counter()
+        slots = pinned.numpy()
+
+        def write(k):
+            p, first = plans[k], sum(len(q.chunks) for q in plans[:k])
+            last = first + len(p.chunks)
+            data = assemble(p, None if statuses is None else statuses[first:last], None if sizes is None else sizes[first:last],
+                            slots[bases[k]:bases[k] + p.slot_bytes])
+            with open(p.path, "wb") as f:
+                f.write(data)
+            return p.path
+        with concurrent.futures.ThreadPoolExecutor(max_workers=self.threads) as pool:
+            written = list(pool.map(write, range(len(plans))))
+        self.host_seconds += time.perf_counter() - t0
+        return written
+
+
+def add_encode_arguments(p):
+    """--exr_encode and --exr_type on a parser that has --exr: both only say how <Pass>.exr is written, so `device` (or `half`) without --exr
+    is a usage error of the parser."""
+    p.add_argument("--exr_encode", default="host", choices=["host", "device"],
+                   help="with --exr, where <Pass>.exr is encoded: by the host writer, or on the device by one pack and one deflate launch for all "
+                        "passes (the host writes headers, offset tables and the bytes it downloads).")
+    p.add_argument("--exr_type", default="float", choices=["float", "half"], help="with --exr, the pixel type of the written channels")
+    inner = p.parse_known_args
+
+    def parse_known_args(args=None, namespace=None):
+        parsed, rest = inner(args, namespace)
+        if parsed.exr_encode == "device" and not parsed.exr:
+            p.error("--exr_encode device needs --exr")
+        if parsed.exr_type != "float" and not parsed.exr:
+            p.error("--exr_type %s needs --exr" % parsed.exr_type)
+        return parsed, rest
+    p.parse_known_args = parse_known_args
+
+
 def add_inflate_argument(p, what):
     """--exr_inflate on a parser that has --exr_decode: the device inflates only into the staged buffer of the device decoder, so `device`
     without --exr_decode device is a usage error of the parser."""
@@ -866,10 +1162,17 @@ def load_frame(directory, architecture, device=None, inflate="host"):
     return features
 
 
-def save_predictions(directory, predictions, as_exr=False):
+def save_predictions(directory, predictions, as_exr=False, encode="host", pixel_type="float"):
     """Prediction.py:483-510 stores every denoised pass and the combined image as <directory>/<Pass>.npy for the Blender side;
-    as_exr additionally writes <Pass>.exr.  `predictions`: the dictionary Predictor.predict_frame returns."""
-    written = []
+    as_exr additionally writes <Pass>.exr.  `predictions`: the dictionary Predictor.predict_frame returns.  encode="device": the .exr
+    files of all passes are encoded by one DeviceEncoder.encode call from the tensors where they are (the same planes); pixel_type "half"
+    writes HALF channels (the values rounded to nearest even, as numpy's astype(float16)), on either path."""
+    if encode not in ("host", "device"):
+        raise ValueError("encode=%r (host or device)" % (encode,))
+    kind = _pixel_type(pixel_type)
+    if not as_exr and (encode == "device" or kind != FLOAT):
+        raise ValueError("encode=%r and pixel_type=%r say how the .exr files are written: they need as_exr" % (encode, pixel_type))
+    written, requests = [], []
     for key, value in predictions.items():
         name = key.split("/", 1)[1] if key.startswith("prediction/") else key
         arr = value.detach().cpu().numpy() if hasattr(value, "detach") else np.asarray(value)
@@ -877,6 +1180,23 @@ def save_predictions(directory, predictions, as_exr=False):
         np.save(path, arr)
         written.append(path)
         if as_exr:
-            write_image(os.path.join(directory, name + ".exr"), arr if arr.shape[-1] == 3 else arr[..., 0])
-            written.append(os.path.join(directory, name + ".exr"))
+            exr = os.path.join(directory, name + ".exr")
+            if encode == "device":
+                if not hasattr(value, "detach"):
+                    raise ValueError("encode='device' takes the predictions as device tensors; %s is none" % key)
+                requests.append((exr, value if value.shape[-1] == 3 else value[..., 0], kind))
+            elif kind == FLOAT:
+                write_image(exr, arr if arr.shape[-1] == 3 else arr[..., 0])
+            else:
+                with np.errstate(over="ignore"):                # (a value past 65504 becomes an infinity: HALF's own rule)
+                    image = np.asarray(arr if arr.shape[-1] == 3 else arr[..., 0], dtype=np.float32).astype(np.float16)
+                write_exr(exr, {"Y": image} if image.ndim == 2 else {c: np.ascontiguousarray(image[..., i]) for i, c in enumerate("RGB")})
+            written.append(exr)
+    if requests:
+        import torch
+        encoder = DeviceEncoder(requests[0][1].device, threads=16)
+        try:
+            encoder.encode([(path, image.to(torch.float32), kind) for path, image, kind in requests])
+        finally:
+            encoder.release()
     return written

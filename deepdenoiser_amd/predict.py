@@ -41,6 +41,7 @@ def parser():
     p.add_argument("--exr_decode", default="host", choices=["host", "device"],
                    help="Where the input EXR files are decoded: on the host, or inflated on the host and rebuilt on the device by one launch.")
     openexr.add_inflate_argument(p, "--exr_decode device")
+    openexr.add_encode_arguments(p)
     p.add_argument("--target", type=str, default=None,
                    help="directory with the ground-truth render of the frame (one .exr per pass): score every denoised pass and Combined against it on "
                         "the device, print one line per pass and write quality.json")
@@ -121,7 +122,7 @@ def main(args):
         scanner = Scanner(arch.device, [(k, tuple(v.shape)) for k, v in frame.items()])
         scanner.scan({k: v.to(arch.device) for k, v in frame.items()})
         report_nonfinite(scanner, args.input, True)
-    for path in openexr.save_predictions(args.input, out, as_exr=args.exr):        # Prediction.py:483-510
+    for path in openexr.save_predictions(args.input, out, as_exr=args.exr, encode=args.exr_encode, pixel_type=args.exr_type):        # Prediction.py:483-510
         print(path)
     if args.target:
         report_quality(args, arch, out)

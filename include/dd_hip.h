@@ -938,6 +938,51 @@ typedef struct { long long src_offset; long long dst_offset; int src_bytes; int 
 int dd_exr_inflate(const dd_exr_stream* streams_host, const dd_exr_stream* streams, int n_streams, const void* src, long src_total,
                    void* staged, long staged_bytes, int* status, dd_stream stream);
 
+/* ---- OpenEXR scan-line chunks packed on the device (csrc/dd_exr_encode.hip): the inverse of dd_exr_reconstruct.  Prediction.py:483-510 stores
+ * every denoised pass as .npy only; the EXR writer of this project replaces openexr.write_exr's host loop (a Python join per scan line, the
+ * numpy predictor and byte split): ONE launch turns the fp32 planes of a whole frame's passes into chunk bytes.
+ *   chunk   : dd_exr_chunk as above: n = rows * row_bytes bytes written to staged + offset (16-byte aligned; the chunk owns the bytes up to
+ *             the next multiple of 16: the padding is written as zero, nothing outside).  The raw bytes are, per row, per file channel in
+ *             name order, that channel's W samples little-endian.  coded != 0: the bytes deflate sees -- t = the even raw bytes, then the odd
+ *             ones ((n + 1) / 2 even bytes), d[0] = t[0], d[i] = t[i] - t[i-1] + 128 (openexr._interleave_and_predict).  coded == 0: the raw
+ *             bytes (NO_COMPRESSION, and chunks stored raw because deflate did not shrink them).
+ *   source  : src fp32 [H, W, C] contiguous; file channel k < n_channels is src[y, x, src_channel[k]] stored as type[k]: 1 HALF (round to
+ *             nearest even, overflow to +-inf, subnormals; every non-NaN input bit-identical to numpy.astype(float16); a NaN stays a NaN),
+ *             2 FLOAT (the bits are moved).  UINT is refused: the planes are fp32.
+ * Both tables are given twice: the HOST copy is validated here, the DEVICE copy is what the kernel reads -- and checks again: a chunk that
+ * does not fit its source or the staged buffer writes nothing.
+ * Refused with a negative status and no launch: NULL tables or buffer while n_chunks > 0, n_chunks < 0, n_sources < 1, a source with a null
+ * plane, H < 1 or W < 1, C outside 1 .. 32, 0 or more than DD_EXR_MAX_CHANNELS channels, a pixel type other than 1 or 2, a src_channel
+ * outside [0, C), rows outside 1 .. 16, a chunk whose file index or rows do not fit its source, an offset that is not 16-byte aligned or
+ * leaves staged_bytes, a staged buffer that is not 16-byte aligned.  n_chunks == 0 is a no-op that returns 0.  No host sync. */
+typedef struct { const float* src; int H; int W; int C; int n_channels; int type[DD_EXR_MAX_CHANNELS]; int src_channel[DD_EXR_MAX_CHANNELS]; } dd_exr_source;
+int dd_exr_pack(const dd_exr_chunk* chunks_host, const dd_exr_chunk* chunks, int n_chunks, const dd_exr_source* sources_host,
+                const dd_exr_source* sources, int n_sources, void* staged, long staged_bytes, dd_stream stream);
+
+/* ---- The packed chunks deflated on the device (csrc/dd_exr_deflate.hip, coder core csrc/dd_deflate_core.h).  Prediction.py:483-510 stores
+ * .npy only; this replaces the zlib.compress call of openexr.write_exr's host loop: ONE launch turns every chunk of a batch into a zlib
+ * stream, one wave per stream.
+ *   stream  : src_bytes bytes at src + src_offset -> a zlib stream (RFC 1950 around RFC 1951, 32 KiB window, the Adler-32 of the source
+ *             bytes) at out + dst_offset (16-byte aligned) of at most dst_capacity bytes.  The host passes src_bytes - 1: a chunk that does
+ *             not shrink is stored raw, the format's own rule.
+ *   status  : DEVICE int[n_streams]; sizes: DEVICE int[n_streams], the stream's bytes when the status is DD_DEFLATE_OK, else 0.
+ *   workspace: DEVICE, dd_exr_deflate_workspace(n_streams) bytes (the token buffers; everything else lives in LDS).
+ * The same input gives the same bytes on every run.  Whatever the status, nothing is written outside the stream's own dst_capacity rounded
+ * up to 16, or outside its own slice of the workspace.  The table is given twice: the HOST copy is validated here, the DEVICE copy is what
+ * the kernel reads -- and checks again (DD_DEFLATE_RECORD).
+ * Refused with a negative status and no launch: NULL pointers while n_streams > 0, n_streams < 0, src_bytes outside 1 .. 1 << 30,
+ * dst_capacity < 0, a source range leaving src_total, a dst_offset that is negative or not 16-byte aligned or whose dst_capacity rounded up
+ * to 16 leaves out_bytes, an output that is not 16-byte aligned, a workspace that is not 4-byte aligned or smaller than
+ * dd_exr_deflate_workspace(n_streams), a source that overlaps the output.  n_streams == 0 is
+ * a no-op that returns 0.  No host sync. */
+#define DD_DEFLATE_OK 0
+#define DD_DEFLATE_RAW 1         /* the stream would not fit dst_capacity: the chunk is stored raw */
+#define DD_DEFLATE_RECORD 2      /* the device copy of the record does not fit the buffers; nothing is read or written through it */
+typedef struct { long long src_offset; long long dst_offset; int src_bytes; int dst_capacity; } dd_exr_deflate_stream;   /* 24 bytes */
+long dd_exr_deflate_workspace(int n_streams);
+int dd_exr_deflate(const dd_exr_deflate_stream* streams_host, const dd_exr_deflate_stream* streams, int n_streams, const void* src, long src_total,
+                   void* out, long out_bytes, void* workspace, long workspace_bytes, int* status, int* sizes, dd_stream stream);
+
 /* 3x3/s2 transpose conv (Tiramisu.py:62-64) = 3x3 SAME conv of the zero-stuffed input with the flipped kernel:
  * y[B,2H,2W,C] = 0 except y[2i+1,2j+1] = x[i,j]; and its adjoint dx[i,j] (+)= dy[2i+1,2j+1] * (mask>0). */
 int dd_zero_stuff(const void* x, int ldx, void* y, int ldy, int C, int B, int H, int W, int dtype, dd_stream stream);
