@@ -271,6 +271,7 @@ class ImportanceUpdateDesc(C.Structure):   # dd_importance_update_desc: a host s
 
 
 EXR_MAX_CHANNELS = 8            # DD_EXR_MAX_CHANNELS
+EXR_MAX_STREAM_BYTES = 1 << 30  # dd_exr_inflate / dd_exr_deflate refuse a stream with more bytes to write / to read
 
 
 class ExrChunk(C.Structure):           # dd_exr_chunk: one scan-line chunk in the staged buffer of dd_exr_reconstruct (24 bytes)

@@ -10,7 +10,7 @@ CRC32C; not gzipped), each a serialized `Event` message (tensorflow/core/util/ev
     HistogramProto (tensorflow/core/framework/summary.proto) { double min = 1, max = 2, num = 3, sum = 4, sum_squares = 5;
                                                                repeated double bucket_limit = 6 [packed], bucket = 7 [packed]; }
 The messages are encoded by hand with the varint helpers of tfrecords.py.  PARITY UNPINNED against TensorBoard itself (none is installed
-here): tests check a round trip and the bytes of a record assembled by hand from the .proto, like tf_checkpoint.py and openexr.py.
+here): tests check a round trip and the bytes of a record assembled by hand from the .proto, like tf_checkpoint.py and openexr/codec.py.
 
 encoded_image_string is a PNG (RFC 2083) written by encode_png: 8-bit gray or RGB, not interlaced, ONE IDAT chunk, filter type 0 on every
 row; decode_png reads exactly that subset.  The PNG side is pinned a little further than the event format: a hand-assembled file in the

@@ -193,6 +193,39 @@ def test_corrupt_files_fail_as_on_the_host_path(files, tmp_path):
     assert np.array_equal(R.bits(results[1][0].cpu().numpy()), R.bits(_want(*good_a)))
 
 
+def test_refused_and_corrupt_files_among_several_batches(files, tmp_path, monkeypatch):
+    """One call of four batches through the ring of two, then two host redos through ring slot 0: a file the device is not given at all
+    (a stream above the limit, here lowered so that a 16-line chunk of 21 pixels is above it; zlib takes it, so its redo ends in a launch) and
+    a file whose last stream holds the wrong number of bytes (its redo ends in the host's ExrError, without a launch)."""
+    by_name = {name: (path, channels) for name, path, channels in files}
+    monkeypatch.setattr(openexr.decode, "MAX_STREAM_BYTES", 4000)
+    refused = by_name["zip_37x21"]
+    assert openexr.plan_file(*refused).source_layout()[4] and not openexr.plan_file(*by_name["zip_5x3"]).source_layout()[4]
+    b = bytearray(open(by_name["zips_37x21"][0], "rb").read())                  # (one line a chunk: none of them is above the limit)
+    last = openexr.plan_file(*by_name["zips_37x21"]).pieces[-1]
+    assert last[2] == 252
+    short = zlib.compress(bytes(100))
+    at = len(b) - len(last[0])
+    struct.pack_into("<i", b, at - 4, len(short))
+    wrong_size = str(tmp_path / "wrong_size.exr")
+    open(wrong_size, "wb").write(bytes(b[:at]) + short)
+    requests = [by_name["zip_5x3"], by_name["zips_5x3"], refused, (wrong_size, 3), by_name["none_5x3"], by_name["zip_5x3"]]
+    plans = [openexr.plan_file(*r) for r in requests]
+    assert [p.source_layout()[4] for p in plans] == [False, False, True, False, False, False]
+    sizes = [p.staged_bytes for p in plans]
+    limit = 9720
+    assert sizes[0] + sizes[1] + sizes[2] > limit >= sizes[2] and sizes[2] + sizes[3] > limit                   # {0, 1} {2: refused, so empty}
+    assert sizes[3] + sizes[4] <= limit < sizes[3] + sizes[4] + sizes[5]                                        # {3, 4} {5}
+    device = openexr.DeviceDecoder("cuda", max_staged_bytes=limit, threads=2, inflate="device")
+    results = device.decode(requests, errors="return")
+    assert device.host_fallbacks == 2
+    assert device.launches == 3 + 1                                 # the three batches that hold a file, and the redo of the refused file
+    assert isinstance(results[3], openexr.ExrError) and "chunk expands to 100 bytes, expected 252" in str(results[3])
+    for k in (0, 1, 2, 4, 5):
+        plane, count = results[k]
+        assert np.array_equal(R.bits(plane.cpu().numpy()), R.bits(_want(*requests[k]))) and count == 0, k
+
+
 # ---------------------------------------------------------------------------------------------------- end to end
 T, SPP, BEST, S = 16, 4, 16, 2
 
