@@ -605,8 +605,8 @@ __global__ __launch_bounds__(WG_WAVES * 64) void compose_stream_wgrad_kernel(con
         q.isg = 0; q.rowb = 1024; q.dst = lds0 + CW_Z6_OFF;
       }
       q.colok = (unsigned)gx < (unsigned)W;
-      // (a strip's last dz6 piece may straddle the image edge: it then carries the next row's first values, which only ever meet zeros --
-      // the a3 row is zero there, and the ones of the bias row are switched off beyond the edge)
+      // (a strip's last dz6 piece may straddle the image edge when W % 8 != 0: it then carries the next row's first values or, behind the last
+      // row of the launch, unwritten scratch; the consumer zeroes what lies beyond the edge)
       q.src = base + ((size_t)(b * H) * W + (q.colok ? gx : 0)) * pxbytes + part * 16;
       return q;
     };
@@ -693,7 +693,13 @@ __global__ __launch_bounds__(WG_WAVES * 64) void compose_stream_wgrad_kernel(con
             af = uint4{px < W ? ONE2 : 0u, px + 2 < W ? ONE2 : 0u, px + 4 < W ? ONE2 : 0u, px + 6 < W ? ONE2 : 0u};
           }
           uint4 bfr = {0u, 0u, 0u, 0u};
-          if (m == 0) bfr = *reinterpret_cast<const uint4*>(z6 + (k * 16 + kh * 8) * 2);
+          if (m == 0) {
+            // values beyond the image edge are zeroed, not left to meet the zeros of the a3 row: behind the last row of the last image they
+            // are scratch memory nobody wrote, and 0 x NaN is NaN
+            const int px = xs + k * 16 + kh * 8;
+            const uint4 z = *reinterpret_cast<const uint4*>(z6 + (k * 16 + kh * 8) * 2);
+            bfr = uint4{px < W ? z.x : 0u, px + 2 < W ? z.y : 0u, px + 4 < W ? z.z : 0u, px + 6 < W ? z.w : 0u};
+          }
           acc[3] = mma32<T>(af, bfr, acc[3]);
         }
       }

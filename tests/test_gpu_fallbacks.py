@@ -64,6 +64,9 @@ CASES = {   # name: (environment of the child, -k expression[, test file (defaul
     # included, on the per-channel-lane colsum_kernel; the same float64 reference, the same bit-equal / elementwise gates
     "pointwise_ops_maxpool_on_the_generic_backward": ({"DD_MAXPOOL_GENERIC": "1"}, "test_maxpool", "test_gpu_pointwise_ops.py"),
     "pointwise_ops_colsum_on_the_per_channel_lane_kernel": ({"DD_COLSUM_VEC": "0"}, "test_colsum", "test_gpu_pointwise_ops.py"),
+    # the op-level compose cases (tests/test_gpu_compose_ops.py) whose ids contain tile_forward: the 16 x 16-tile forward of csrc/dd_compose.hip
+    # stage by stage against the float64 reference and gates of tests/compose_ref.py (in a default process those ids skip: the switch is read once)
+    "compose_ops_tile_forward": ({"DD_COMPOSE_STREAM": "0"}, "tile_forward", "test_gpu_compose_ops.py"),
 }
 
 

@@ -752,44 +752,20 @@ def test_compose_net_backward_streaming_op_level(dtype, shape):
     if not torch.cuda.is_available():
         pytest.skip("no GPU")
     import ctypes as C
+    import compose_ref
     from deepdenoiser_amd import _lib as L
-    from oracle import model as OM
     lib = L.load()
     N, H, W = shape
     tdt = {"bf16": torch.bfloat16, "f16": torch.float16}[dtype]
-    g = torch.Generator().manual_seed(11 + N + H + W)
-    vs = OM.VarStore(torch.float64, seed=5, storage=dtype)
-    vs.enter_scope("s")
-    recorded = []
-    conv2d = vs.conv2d
-
-    def recording(*a, **k):
-        y = conv2d(*a, **k)
-        recorded.append(y)
-        return y
-    vs.conv2d = recording
-    small = (torch.randn(N, H // 2, W // 2, 3, generator=g, dtype=torch.float64) * 0.7).float().double().requires_grad_(True)
-    fine = (torch.randn(N, H, W, 3, generator=g, dtype=torch.float64) * 0.7).float().double().requires_grad_(True)
-    gout = torch.randn(N, H, W, 3, generator=g, dtype=torch.float64).float().double()
-    out = OM.compose_scales(vs, "s", small, fine)
-    for name, v in vs.vars.items():      # glorot kernels, and biases away from zero (as after some training)
-        if name.endswith("/bias"):
-            with torch.no_grad():
-                v.copy_(torch.randn(v.shape, generator=g, dtype=torch.float64) * 0.1)
-    recorded.clear()
-    vs.enter_scope("s")
-    out = OM.compose_scales(vs, "s", small, fine)
-    names = list(vs.vars)
-    grads = torch.autograd.grad((out * gout).sum(), [small, fine] + [vs.vars[n] for n in names])
-    a1, r1, a2, r3, a3, wl = [t.detach() for t in recorded]
-    acts = [a1, torch.relu(r1), a2, torch.relu(r3), a3]
+    ref = compose_ref.backward_reference(shape, dtype)      # the teacher-forced reference, shared with tests/test_gpu_compose_ops.py
+    names, grads = ref["names"], ref["grads"]
     dev = "cuda"
-    keep = [t.to(dev, tdt).contiguous() for t in acts] + [wl.to(dev, tdt).contiguous()]
-    w32 = {n: vs.vars[n].detach().float().to(dev).contiguous() for n in names}
+    keep = [t.to(dev, tdt).contiguous() for t in ref["acts"]] + [ref["wl"].to(dev, tdt).contiguous()]
+    w32 = {n: ref["vars"][n].float().to(dev).contiguous() for n in names}
     dws = {n: torch.zeros_like(w32[n]) for n in names}
     d_small = torch.zeros(N, H // 2, W // 2, 3, device=dev)
     d_fine = torch.zeros(N, H, W, 3, device=dev)
-    sm, fi, go = small.detach().float().to(dev), fine.detach().float().to(dev), gout.float().to(dev)
+    sm, fi, go = ref["small"].float().to(dev), ref["fine"].float().to(dev), ref["gout"].float().to(dev)
     cb = L.ComposeBwdArgs()
     C.memset(C.byref(cb), 0, C.sizeof(cb))
     cb.small, cb.ld_small, cb.fine, cb.ld_fine, cb.dout, cb.ld_dout = sm.data_ptr(), 3, fi.data_ptr(), 3, go.data_ptr(), 3
