@@ -52,7 +52,7 @@ SYMBOLS = (
     "dd_nonfinite_scan", "dd_nonfinite_repair", "dd_frame_quality_scratch_bytes", "dd_frame_quality", "dd_stitch_blend",
     "dd_grad_norms", "dd_adam_step_clipped", "dd_adam_step_scaled_clipped", "dd_sample_tiles",
     "dd_tile_statistics", "dd_importance_cells", "dd_importance_update", "dd_exr_reconstruct", "dd_exr_inflate",
-    "dd_exr_pack", "dd_exr_deflate_workspace", "dd_exr_deflate",
+    "dd_exr_pack", "dd_exr_deflate_workspace", "dd_exr_deflate", "dd_png_pack", "dd_png_deflate_workspace", "dd_png_deflate",
 )
 
 
@@ -296,7 +296,24 @@ class ExrDeflateStream(C.Structure):   # dd_exr_deflate_stream: one packed chunk
     _fields_ = [("src_offset", C.c_longlong), ("dst_offset", C.c_longlong), ("src_bytes", C.c_int), ("dst_capacity", C.c_int)]
 
 
-# DD_DEFLATE_*: the per-stream status codes of dd_exr_deflate
+PNG_MAX_ROW_BYTES, PNG_STAGE_BYTES = 12288, 36864      # DD_PNG_MAX_ROW_BYTES, DD_PNG_STAGE_BYTES: what the pack kernel holds in LDS
+
+
+class PngImage(C.Structure):           # dd_png_image: the fp32 plane a PNG is packed from, its sample channels and the exposure (40 bytes)
+    _fields_ = [("src", C.c_void_p), ("H", C.c_int), ("W", C.c_int), ("C", C.c_int), ("n_channels", C.c_int), ("src_channel", C.c_int * 3),
+                ("exposure", C.c_float)]
+
+
+class PngSegment(C.Structure):         # dd_png_segment: rows y0 .. y0 + rows of an image and the slot of their filtered bytes (24 bytes)
+    _fields_ = [("offset", C.c_longlong), ("image", C.c_int), ("y0", C.c_int), ("rows", C.c_int), ("reserved", C.c_int)]
+
+
+class PngStream(C.Structure):          # dd_png_stream: one packed segment of dd_png_deflate and the slot of its raw-deflate body (32 bytes)
+    _fields_ = [("src_offset", C.c_longlong), ("dst_offset", C.c_longlong), ("src_bytes", C.c_int), ("dst_capacity", C.c_int), ("last", C.c_int),
+                ("reserved", C.c_int)]
+
+
+# DD_DEFLATE_*: the per-stream status codes of dd_exr_deflate and dd_png_deflate
 DEFLATE_OK, DEFLATE_RAW, DEFLATE_RECORD = range(3)
 DEFLATE_STATUS_NAMES = ("OK", "RAW", "RECORD")
 DEFLATE_BLOCK_TOKENS = 16384     # DD_DEFLATE_BLOCK_TOKENS (csrc/dd_deflate_core.h): 32-bit tokens per stream in the workspace
@@ -513,6 +530,10 @@ def load():
     lib.dd_exr_deflate_workspace.argtypes = [i]
     lib.dd_exr_deflate_workspace.restype = l
     lib.dd_exr_deflate.argtypes = [vp, vp, i, vp, l, vp, l, vp, l, vp, vp, vp]
+    lib.dd_png_pack.argtypes = [vp, vp, i, vp, vp, i, vp, vp, l, vp]
+    lib.dd_png_deflate_workspace.argtypes = [i]
+    lib.dd_png_deflate_workspace.restype = l
+    lib.dd_png_deflate.argtypes = [vp, vp, i, vp, l, vp, l, vp, l, vp, vp, vp, vp]
     _lib = lib
     return lib
 

@@ -28,9 +28,18 @@
 //             that is smaller (few used symbols), zero runs as the symbols 17 / 18 in two bits and every other length in five.  The sizes
 //             of the dynamic and of the fixed form follow exactly from the histograms; the smaller is written.
 //   emit    : 64 items (tokens, or header fields) per step: bit lengths, a prefix sum, every lane ORs its bits (at most 48) into an LDS window,
-//             whole words are stored in order.  Before every store the bytes still to come (at least the four of the Adler-32) are checked
-//             against dst_capacity: running out is DD_DEFLATE_RAW, never a write past the slot.
+//             whole words are stored in order.  Before every store the bytes still to come (at least the framing's trailer: the four of the
+//             Adler-32, or of a segment's marker, see Framings) are checked against dst_capacity: running out is DD_DEFLATE_RAW, never a
+//             write past the slot.
 //   adler   : sums of the SOURCE bytes by the lanes, 16 bytes per lane and step, kept in 64 bits (dd_exr_inflate.hip has the same form).
+//
+// Framings.  DD_DEFLATE_FRAME_ZLIB (dd_deflate_stream, the EXR chunks): the two header bytes 78 01, the blocks (the last one final), padding to
+// the byte border, the Adler-32.  DD_DEFLATE_FRAME_SEGMENT / _LAST_SEGMENT (dd_deflate_segment, the pieces of a PNG's one IDAT stream,
+// dd_png_encode.hip): a raw-deflate body without header; the Adler-32 of the source goes back to the caller, who combines the pieces'.  A
+// segment that is not the last has no final block and ends with an EMPTY STORED block -- three zero bits, padding to the byte border, 00 00 FF FF
+// (what zlib's Z_SYNC_FLUSH writes) -- so it ends on a byte border and the next body follows it directly; the last segment's last block is
+// final and padded to the byte border.  A segment is one block until the token buffer is full (no border between two halves: filtered image
+// rows have none).  The emitter's reserve (below) is the four marker bytes for a segment that is not the last and nothing for the last one.
 #ifndef DD_DEFLATE_CORE_H
 #define DD_DEFLATE_CORE_H
 
@@ -265,6 +274,7 @@ struct dd_deflate_emitter {
   int fill;         // bits of window[0] that are taken (<= 32)
   int written;      // bytes stored
   int capacity;
+  int reserve;      // bytes that are certain to follow the call at hand (the Adler-32, the marker of a segment): a store is made only where they still fit
 };
 
 // The lanes have set ws->item[lane] (bits, low end first) and ws->scan[lane] (how many, <= 48).  `last`: nothing follows (the bits end on a
@@ -286,8 +296,8 @@ DD_DHD bool dd_deflate_emit(dd_deflate_state* ws, dd_deflate_emitter& em, Out& o
   }
   const int total = em.fill + (int)ws->scan[DD_DEFLATE_LANES - 1], full = total >> 5;
   DD_LANES_SYNC();
-  // what is still to come: the rest of this word and, unless this is the last call, at least the Adler-32
-  const int tail = last ? ((total & 31) + 7) >> 3 : 4;
+  // what is still to come: the rest of this word and, unless this is the last call, at least the framing's trailer (em.reserve)
+  const int tail = last ? ((total & 31) + 7) >> 3 : em.reserve;
   if (em.written > em.capacity - 4 * full - tail) return false;
   DD_FOR_LANES(lane) {
     for (int w = lane; w < full; w += DD_DEFLATE_LANES) out.word(em.written + 4 * w, ws->window[w]);
@@ -512,22 +522,31 @@ DD_DHD int dd_match_length(const unsigned char* src, int c, int p, int limit) {
 }
 
 // ---------------------------------------------------------------------------------------------------- one stream
-// src[0 .. n) -> a zlib stream of at most `capacity` bytes through `out`; tokens: DD_DEFLATE_BLOCK_TOKENS words of workspace.
-// -> DD_DEFLATE_OK and *size, or DD_DEFLATE_RAW (then anything may stand in out[0 .. capacity), nothing behind it).
+#define DD_DEFLATE_FRAME_ZLIB 0
+#define DD_DEFLATE_FRAME_SEGMENT 1
+#define DD_DEFLATE_FRAME_LAST_SEGMENT 2
+
+// src[0 .. n) -> a stream in `framing` of at most `capacity` bytes through `out`; tokens: DD_DEFLATE_BLOCK_TOKENS words of workspace.
+// -> DD_DEFLATE_OK and *size, or DD_DEFLATE_RAW (then anything may stand in out[0 .. capacity), nothing behind it).  *adler: the Adler-32 of
+// the source, for the segment framings whatever the status (the ZLIB framing writes it into the stream and sets it only with OK).
 template <class Out>
-DD_DHD int dd_deflate_stream(const unsigned char* src, int n, int capacity, unsigned* tokens, dd_deflate_state* ws, Out& out, int* size) {
+DD_DHD int dd_deflate_framed(const int framing, const unsigned char* src, int n, int capacity, unsigned* tokens, dd_deflate_state* ws, Out& out, int* size,
+                             unsigned* adler_out) {
+  const bool zlib = framing == DD_DEFLATE_FRAME_ZLIB, final_stream = framing != DD_DEFLATE_FRAME_SEGMENT;
   *size = 0;
-  if (capacity < 8) return DD_DEFLATE_RAW;      // (two header bytes, at least a 10-bit block, the Adler-32)
+  if (!zlib) *adler_out = dd_deflate_adler(ws, src, n);
+  // (ZLIB: two header bytes, at least a 10-bit block, the Adler-32; a segment: the block, and the three bits and four bytes of its marker)
+  if (capacity < (zlib ? 8 : (final_stream ? 2 : 6))) return DD_DEFLATE_RAW;
   DD_FOR_LANES(lane) {
     for (int i = lane; i < (1 << DD_DEFLATE_HASH_BITS); i += DD_DEFLATE_LANES) ws->hash[i] = 0u;
     for (int i = lane; i < DD_DEFLATE_WINDOW_WORDS; i += DD_DEFLATE_LANES) ws->window[i] = 0u;
     for (int i = lane; i < DD_DEFLATE_LIT + DD_DEFLATE_DIST; i += DD_DEFLATE_LANES) ws->hist[i] = i == 256 ? 1u : 0u;
   }
   DD_LANES_SYNC();
-  ws->window[0] = 0x0178u;      // CMF 0x78 (deflate, 32 KiB window), FLG 0x01 (fastest; 0x7801 % 31 == 0)
-  dd_deflate_emitter em{16, 0, capacity};
+  if (zlib) ws->window[0] = 0x0178u;      // CMF 0x78 (deflate, 32 KiB window), FLG 0x01 (fastest; 0x7801 % 31 == 0)
+  dd_deflate_emitter em{zlib ? 16 : 0, 0, capacity, framing == DD_DEFLATE_FRAME_LAST_SEGMENT ? 0 : 4};
   DD_LANES_SYNC();
-  const int half = n >= DD_DEFLATE_SPLIT_BYTES ? (n + 1) >> 1 : n;      // (a short stream is one block: a second header costs more than it wins)
+  const int half = (zlib && n >= DD_DEFLATE_SPLIT_BYTES) ? (n + 1) >> 1 : n;      // (a short stream is one block: a second header costs more than it wins)
   int pos = 0, carry = 0, ntok = 0, block_start = 0;
   while (pos < n) {
     int end = pos + DD_DEFLATE_LANES < n ? pos + DD_DEFLATE_LANES : n;
@@ -615,7 +634,7 @@ DD_DHD int dd_deflate_stream(const unsigned char* src, int n, int capacity, unsi
     pos = carry > end ? carry : end;
     const bool more = pos < n;
     if (!more || ntok + DD_DEFLATE_LANES > DD_DEFLATE_BLOCK_TOKENS || (block_start < half && pos >= half)) {
-      if (!dd_deflate_block(ws, tokens, ntok, !more, em, out)) return DD_DEFLATE_RAW;
+      if (!dd_deflate_block(ws, tokens, ntok, !more && final_stream, em, out)) return DD_DEFLATE_RAW;
       DD_FOR_LANES(lane) {
         for (int s = lane; s < DD_DEFLATE_LIT + DD_DEFLATE_DIST; s += DD_DEFLATE_LANES) ws->hist[s] = s == 256 ? 1u : 0u;
       }
@@ -624,16 +643,49 @@ DD_DHD int dd_deflate_stream(const unsigned char* src, int n, int capacity, unsi
       block_start = pos;
     }
   }
-  // ---- up to the byte border, then the Adler-32 of the source, high byte first
-  const unsigned adler = dd_deflate_adler(ws, src, n);
-  em.fill = (em.fill + 7) & ~7;
-  DD_FOR_LANES(lane) {
-    ws->item[lane] = lane == 0 ? (unsigned long long)((adler >> 24) | ((adler >> 8) & 0xff00u) | ((adler << 8) & 0xff0000u) | (adler << 24)) : 0ull;
-    ws->scan[lane] = lane == 0 ? 32u : 0u;
+  if (zlib) {
+    // ---- up to the byte border, then the Adler-32 of the source, high byte first
+    const unsigned adler = dd_deflate_adler(ws, src, n);
+    em.fill = (em.fill + 7) & ~7;
+    DD_FOR_LANES(lane) {
+      ws->item[lane] = lane == 0 ? (unsigned long long)((adler >> 24) | ((adler >> 8) & 0xff00u) | ((adler << 8) & 0xff0000u) | (adler << 24)) : 0ull;
+      ws->scan[lane] = lane == 0 ? 32u : 0u;
+    }
+    if (!dd_deflate_emit(ws, em, out, true)) return DD_DEFLATE_RAW;
+    *adler_out = adler;
+  } else if (final_stream) {
+    // ---- the final block is behind: up to the byte border, nothing more
+    em.fill = (em.fill + 7) & ~7;
+    DD_FOR_LANES(lane) {
+      ws->item[lane] = 0ull;
+      ws->scan[lane] = 0u;
+    }
+    if (!dd_deflate_emit(ws, em, out, true)) return DD_DEFLATE_RAW;
+  } else {
+    // ---- an empty stored block that is not final: BFINAL 0 and BTYPE 00, zero bits up to the byte border, LEN 0000 and NLEN FFFF
+    const unsigned zeros = 3u + ((0u - ((unsigned)em.fill + 3u)) & 7u);
+    DD_FOR_LANES(lane) {
+      ws->item[lane] = lane == 1 ? 0xffff0000ull : 0ull;
+      ws->scan[lane] = lane == 0 ? zeros : (lane == 1 ? 32u : 0u);
+    }
+    if (!dd_deflate_emit(ws, em, out, true)) return DD_DEFLATE_RAW;
   }
-  if (!dd_deflate_emit(ws, em, out, true)) return DD_DEFLATE_RAW;
   *size = em.written;
   return DD_DEFLATE_OK;
+}
+
+// a zlib stream (RFC 1950): what dd_exr_deflate writes per chunk
+template <class Out>
+DD_DHD int dd_deflate_stream(const unsigned char* src, int n, int capacity, unsigned* tokens, dd_deflate_state* ws, Out& out, int* size) {
+  unsigned adler;
+  return dd_deflate_framed(DD_DEFLATE_FRAME_ZLIB, src, n, capacity, tokens, ws, out, size, &adler);
+}
+
+// one segment of a zlib stream that the caller puts together (dd_png_deflate): a raw-deflate body and the segment's Adler-32
+template <class Out>
+DD_DHD int dd_deflate_segment(const unsigned char* src, int n, int capacity, bool last, unsigned* tokens, dd_deflate_state* ws, Out& out, int* size,
+                              unsigned* adler) {
+  return dd_deflate_framed(last ? DD_DEFLATE_FRAME_LAST_SEGMENT : DD_DEFLATE_FRAME_SEGMENT, src, n, capacity, tokens, ws, out, size, adler);
 }
 
 #endif  // DD_DEFLATE_CORE_H

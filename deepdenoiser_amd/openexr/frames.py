@@ -144,17 +144,23 @@ def load_frame(directory, architecture, device=None, inflate="host"):
     return features
 
 
-def save_predictions(directory, predictions, as_exr=False, encode="host", pixel_type="float"):
+def save_predictions(directory, predictions, as_exr=False, encode="host", pixel_type="float", png=False, png_encode="host", exposure=1.0):
     """Prediction.py:483-510 stores every denoised pass and the combined image as <directory>/<Pass>.npy for the Blender side;
     as_exr additionally writes <Pass>.exr.  `predictions`: the dictionary Predictor.predict_frame returns.  encode="device": the .exr
     files of all passes are encoded by one DeviceEncoder.encode call from the tensors where they are (the same planes); pixel_type "half"
-    writes HALF channels (the values rounded to nearest even, as numpy's astype(float16)), on either path."""
+    writes HALF channels (the values rounded to nearest even, as numpy's astype(float16)), on either path.  png additionally writes
+    <Pass>.png, the 8-bit sRGB picture of the pass times `exposure` (png.py): png_encode="host" by numpy and zlib, "device" by one
+    DevicePngEncoder.encode call from the tensors where they are (the same pixels).  With png=False nothing changes."""
+    if png_encode not in ("host", "device"):
+        raise ValueError("png_encode=%r (host or device)" % (png_encode,))
+    if not png and png_encode == "device":
+        raise ValueError("png_encode=%r says how the .png files are written: it needs png" % (png_encode,))
     if encode not in ("host", "device"):
         raise ValueError("encode=%r (host or device)" % (encode,))
     kind = _pixel_type(pixel_type)
     if not as_exr and (encode == "device" or kind != FLOAT):
         raise ValueError("encode=%r and pixel_type=%r say how the .exr files are written: they need as_exr" % (encode, pixel_type))
-    written, requests = [], []
+    written, requests, pictures = [], [], []
     for key, value in predictions.items():
         name = key.split("/", 1)[1] if key.startswith("prediction/") else key
         arr = value.detach().cpu().numpy() if hasattr(value, "detach") else np.asarray(value)
@@ -174,6 +180,8 @@ def save_predictions(directory, predictions, as_exr=False, encode="host", pixel_
                     image = np.asarray(arr if arr.shape[-1] == 3 else arr[..., 0], dtype=np.float32).astype(np.float16)
                 write_exr(exr, _image_planes(image))
             written.append(exr)
+        if png:
+            pictures.append((name, value if png_encode == "device" else arr))
     if requests:
         import torch
         encoder = DeviceEncoder(requests[0][1].device, threads=16)
@@ -181,4 +189,7 @@ def save_predictions(directory, predictions, as_exr=False, encode="host", pixel_
             encoder.encode([(path, image.to(torch.float32), kind) for path, image, kind in requests])
         finally:
             encoder.release()
+    if pictures:
+        from ..png import save_pngs
+        written += save_pngs(directory, pictures, encode=png_encode, exposure=exposure)
     return written

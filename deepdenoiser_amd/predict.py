@@ -9,7 +9,7 @@ import os
 import numpy as np
 import torch
 
-from . import openexr, tf_checkpoint
+from . import openexr, png, tf_checkpoint
 from .architecture import Architecture
 from .nonfinite import Scanner, mask_to_rgb
 from .prediction import Predictor
@@ -42,10 +42,13 @@ def parser():
                    help="Where the input EXR files are decoded: on the host, or inflated on the host and rebuilt on the device by one launch.")
     openexr.add_inflate_argument(p, "--exr_decode device")
     openexr.add_encode_arguments(p)
+    png.add_png_arguments(p)
     p.add_argument("--target", type=str, default=None,
                    help="directory with the ground-truth render of the frame (one .exr per pass): score every denoised pass and Combined against it on "
                         "the device, print one line per pass and write quality.json")
-    p.add_argument("--exposure", type=float, default=1.0, help="--target: factor in front of the 8-bit sRGB quantisation of psnr_8bit and ssim")
+    p.add_argument("--exposure", type=float, default=1.0,
+                   help="factor in front of the 8-bit sRGB quantisation: of the pictures --png writes, and of psnr_8bit and ssim of --target (which are "
+                        "computed on exactly those pictures)")
     p.add_argument("--quality_json", type=str, default=None, help="--target: where to write the figures (default: quality.json next to the inputs)")
     p.add_argument("--ssim_png", action="store_true", help="--target: write <Pass>_ssim.png, the SSIM map (gray; magenta: a window with a NaN / Inf pixel)")
     return p
@@ -122,7 +125,8 @@ def main(args):
         scanner = Scanner(arch.device, [(k, tuple(v.shape)) for k, v in frame.items()])
         scanner.scan({k: v.to(arch.device) for k, v in frame.items()})
         report_nonfinite(scanner, args.input, True)
-    for path in openexr.save_predictions(args.input, out, as_exr=args.exr, encode=args.exr_encode, pixel_type=args.exr_type):        # Prediction.py:483-510
+    for path in openexr.save_predictions(args.input, out, as_exr=args.exr, encode=args.exr_encode, pixel_type=args.exr_type, png=args.png,
+                                         png_encode=args.png_encode, exposure=args.exposure):        # Prediction.py:483-510
         print(path)
     if args.target:
         report_quality(args, arch, out)

@@ -983,6 +983,55 @@ long dd_exr_deflate_workspace(int n_streams);
 int dd_exr_deflate(const dd_exr_deflate_stream* streams_host, const dd_exr_deflate_stream* streams, int n_streams, const void* src, long src_total,
                    void* out, long out_bytes, void* workspace, long workspace_bytes, int* status, int* sizes, dd_stream stream);
 
+/* ---- Denoised passes as 8-bit sRGB PNGs, packed on the device (csrc/dd_png_encode.hip, row coder csrc/dd_png_core.h).  Prediction.py:483-510
+ * stores every denoised pass as .npy only, and its own PNG line (the commented-out `cv2.imwrite(... + '/combined.png', ...)` behind that block,
+ * :514-517) never runs; this replaces it: ONE launch turns the fp32 planes of all passes of a frame into FILTERED PNG rows, cut into segments of whole rows.
+ *   image   : src fp32 [H, W, C] contiguous; n_channels 3 (RGB, colour type 2) or 1 (gray, colour type 0); byte k of a pixel is
+ *             src[y, x, src_channel[k]] * exposure (one fp32 multiply) counted against `thresholds`, DEVICE float[255], the table of
+ *             metrics.preview_thresholds that dd_loss_previews takes: byte = number of entries <= v (-inf, negatives, -0.0 -> 0, +inf -> 255).
+ *             A NaN in any channel makes an RGB pixel (255, 0, 255), a NaN gray sample 0.
+ *   segment : rows y0 .. y0 + rows of image `image`: n = rows * (1 + W * n_channels) bytes -- per row the filter type (0 None, 1 Sub, 2 Up,
+ *             3 Average, 4 Paeth: the one with the smallest sum of |filtered byte as signed 8-bit|, ties to the lowest number; the row above
+ *             row 0 is zeros) and the filtered bytes -- written to staged + offset (16-byte aligned; the segment owns the bytes up to the next
+ *             multiple of 16: the padding is written as zero, nothing outside).  W * n_channels <= DD_PNG_MAX_ROW_BYTES and
+ *             n <= DD_PNG_STAGE_BYTES: a segment is staged in the workgroup's LDS.
+ * Both tables are given twice: the HOST copy is validated here, the DEVICE copy is what the kernel reads -- and checks again: a segment that
+ * does not fit its image or the staged buffer writes nothing.
+ * Refused with a negative status and no launch: NULL tables, thresholds or buffer while n_segments > 0, n_segments < 0, n_images < 1,
+ * staged_bytes < 16, an image with a null plane, H < 1 or W < 1, C outside 1 .. 32, n_channels other than 1 or 3, a src_channel outside
+ * [0, C), a row of more than DD_PNG_MAX_ROW_BYTES bytes, a plane that overlaps the staged buffer, a segment whose image index or rows do not
+ * fit its image or whose bytes exceed DD_PNG_STAGE_BYTES, an offset that is not 16-byte aligned or leaves staged_bytes, a staged buffer that
+ * is not 16-byte aligned, thresholds that are not 4-byte aligned.  n_segments == 0 is a no-op that returns 0.  No host sync. */
+#define DD_PNG_MAX_ROW_BYTES 12288   /* W * n_channels of an image: two row buffers of this size in LDS */
+#define DD_PNG_STAGE_BYTES 36864     /* the bytes of a segment: the staging buffer in LDS */
+typedef struct { const float* src; int H; int W; int C; int n_channels; int src_channel[3]; float exposure; } dd_png_image;   /* 40 bytes */
+typedef struct { long long offset; int image; int y0; int rows; int reserved; } dd_png_segment;                              /* 24 bytes */
+int dd_png_pack(const dd_png_segment* segments_host, const dd_png_segment* segments, int n_segments, const dd_png_image* images_host,
+                const dd_png_image* images, int n_images, const float* thresholds, void* staged, long staged_bytes, dd_stream stream);
+
+/* ---- The packed segments deflated on the device (csrc/dd_png_encode.hip, coder core csrc/dd_deflate_core.h in its segment framing).
+ * Prediction.py:483-510 stores .npy only (its PNG line, the commented-out `cv2.imwrite(... + '/combined.png', ...)` at :514-517, would have
+ * compressed on the host); ONE launch turns every segment of every pass into a raw-deflate body (RFC 1951), one wave per segment.  The bodies of a file's
+ * segments, in order, behind the two bytes 78 01 and in front of the Adler-32 of all filtered bytes, are the zlib stream of its IDAT chunk.
+ *   stream  : src_bytes bytes at src + src_offset -> at most dst_capacity bytes at out + dst_offset (16-byte aligned).  last == 0: no block
+ *             is final and the body ends with an empty stored block (three zero bits, zero bits up to the byte border, 00 00 FF FF), so it
+ *             ends on a byte border; last == 1: the last block is final and padded to the byte border.  The host passes src_bytes - 1: a
+ *             segment that does not shrink (DD_DEFLATE_RAW) is written as stored blocks by the host.
+ *   status  : DEVICE int[n_streams] (DD_DEFLATE_*); sizes: DEVICE int[n_streams], the body's bytes when the status is DD_DEFLATE_OK, else 0;
+ *   adler   : DEVICE unsigned[n_streams], the Adler-32 of the stream's source bytes when the status is OK or RAW (the host combines them).
+ *   workspace: DEVICE, dd_png_deflate_workspace(n_streams) bytes.
+ * The same input gives the same bytes on every run.  Whatever the status, nothing is written outside the stream's own dst_capacity rounded up
+ * to 16, or outside its own slice of the workspace.  The table is given twice: the HOST copy is validated here, the DEVICE copy is what the
+ * kernel reads -- and checks again (DD_DEFLATE_RECORD).
+ * Refused with a negative status and no launch: NULL pointers while n_streams > 0, n_streams < 0, src_bytes outside 1 .. 1 << 30,
+ * dst_capacity < 0, last other than 0 or 1, a source range leaving src_total, a dst_offset that is negative or not 16-byte aligned or whose
+ * dst_capacity rounded up to 16 leaves out_bytes, an output that is not 16-byte aligned, a workspace that is not 4-byte aligned or smaller
+ * than dd_png_deflate_workspace(n_streams), a source that overlaps the output.  n_streams == 0 is a no-op that returns 0.  No host sync. */
+typedef struct { long long src_offset; long long dst_offset; int src_bytes; int dst_capacity; int last; int reserved; } dd_png_stream;   /* 32 bytes */
+long dd_png_deflate_workspace(int n_streams);
+int dd_png_deflate(const dd_png_stream* streams_host, const dd_png_stream* streams, int n_streams, const void* src, long src_total, void* out,
+                   long out_bytes, void* workspace, long workspace_bytes, int* status, int* sizes, unsigned* adler, dd_stream stream);
+
 /* 3x3/s2 transpose conv (Tiramisu.py:62-64) = 3x3 SAME conv of the zero-stuffed input with the flipped kernel:
  * y[B,2H,2W,C] = 0 except y[2i+1,2j+1] = x[i,j]; and its adjoint dx[i,j] (+)= dy[2i+1,2j+1] * (mask>0). */
 int dd_zero_stuff(const void* x, int ldx, void* y, int ldy, int C, int B, int H, int W, int dtype, dd_stream stream);
