@@ -22,6 +22,7 @@ PREVIEW_SOURCE, PREVIEW_PREDICTION, PREVIEW_TARGET, PREVIEW_DIFFERENCE = 1, 2, 4
 PREVIEW_MAX_IMAGES, PREVIEW_THRESHOLDS = 16, 255
 NONFINITE_MAX_PLANES = 32      # DD_NONFINITE_MAX_PLANES
 QUALITY_MAX_PAIRS, QUALITY_TILE = 32, 32      # DD_QUALITY_MAX_PAIRS, DD_QUALITY_TILE
+TEMPORAL_MAX_PASSES, TEMPORAL_MAX_GUIDES, TEMPORAL_TILE = 32, 4, 16      # DD_TEMPORAL_MAX_PASSES, DD_TEMPORAL_MAX_GUIDES, DD_TEMPORAL_TILE
 GRAD_CHUNK, GRAD_PARTIAL_BYTES = 4096, 24      # DD_GRAD_CHUNK, DD_GRAD_PARTIAL_BYTES
 
 
@@ -53,6 +54,7 @@ SYMBOLS = (
     "dd_grad_norms", "dd_adam_step_clipped", "dd_adam_step_scaled_clipped", "dd_sample_tiles",
     "dd_tile_statistics", "dd_importance_cells", "dd_importance_update", "dd_exr_reconstruct", "dd_exr_inflate",
     "dd_exr_pack", "dd_exr_deflate_workspace", "dd_exr_deflate", "dd_png_pack", "dd_png_deflate_workspace", "dd_png_deflate",
+    "dd_temporal_scratch_bytes", "dd_temporal_stabilize",
 )
 
 
@@ -386,6 +388,21 @@ class QualityRecord(C.Structure):       # dd_quality_record: what dd_frame_quali
                 ("max_abs", C.c_float), ("reserved", C.c_float)]
 
 
+class TemporalPass(C.Structure):        # dd_temporal_pass (40 bytes)
+    _fields_ = [("current", C.c_void_p), ("history", C.c_void_p), ("out", C.c_void_p), ("current_ld", C.c_int), ("history_ld", C.c_int),
+                ("out_ld", C.c_int), ("nch", C.c_int)]
+
+
+class TemporalGuide(C.Structure):       # dd_temporal_guide (32 bytes)
+    _fields_ = [("current", C.c_void_p), ("previous", C.c_void_p), ("current_ld", C.c_int), ("previous_ld", C.c_int), ("nch", C.c_int),
+                ("tolerance", C.c_float)]
+
+
+class TemporalRecord(C.Structure):      # dd_temporal_record: what dd_temporal_stabilize leaves per pass in device memory (64 bytes)
+    _fields_ = [("pixels_offscreen", C.c_uint64), ("pixels_guide", C.c_uint64), ("pixels_nonfinite", C.c_uint64), ("pixels_blended", C.c_uint64),
+                ("values_clamped", C.c_uint64), ("change", C.c_double), ("flicker_before", C.c_double), ("flicker_after", C.c_double)]
+
+
 _lib = None
 
 
@@ -534,6 +551,9 @@ def load():
     lib.dd_png_deflate_workspace.argtypes = [i]
     lib.dd_png_deflate_workspace.restype = l
     lib.dd_png_deflate.argtypes = [vp, vp, i, vp, l, vp, l, vp, l, vp, vp, vp, vp]
+    lib.dd_temporal_scratch_bytes.argtypes = [i, i, i]
+    lib.dd_temporal_scratch_bytes.restype = l
+    lib.dd_temporal_stabilize.argtypes = [C.POINTER(TemporalPass), i, C.POINTER(TemporalGuide), i, i, i, vp, i, f, f, f, f, vp, vp, vp]
     _lib = lib
     return lib
 

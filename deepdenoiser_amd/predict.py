@@ -1,6 +1,8 @@
 """`python -m deepdenoiser_amd.predict architecture.json --input <frame directory>` -- the reference's `python Prediction.py architecture.json
 --input dir` (TensorFlow/Prediction.py:23-53 argument set, :188-520 main): the directory's per-pass .exr files -> halo tiles -> forward on the
-MI355X path (fp16 MFMA by default) -> crop / stitch / recombination -> <Pass>.npy and Combined.npy next to the inputs."""
+MI355X path (fp16 MFMA by default) -> crop / stitch / recombination -> <Pass>.npy and Combined.npy next to the inputs.
+`--input_sequence <parent directory>` denoises every frame directory below it in one process with one Predictor; `--temporal` stabilises the
+predicted passes of each frame against the previous one before the recombination (temporal.py, DESIGN 3.31: the reference has no such step)."""
 import argparse
 import json
 import multiprocessing
@@ -20,6 +22,21 @@ def parser():
     p = argparse.ArgumentParser(description="Prediction for the DeepDenoiser (MI355X-native hot path).")
     p.add_argument("json_filename", help="The json specifying all the relevant details.")
     p.add_argument("--input", type=str, help="Make a prediction for the files in this directory.")
+    p.add_argument("--input_sequence", type=str, default=None,
+                   help="Denoise a frame sequence in one process: every sub-directory of this directory that holds .exr files is a frame, ordered by the "
+                        "integers in its name, then by name.  Every per-frame option applies to each frame; the outputs go into each frame directory.")
+    p.add_argument("--temporal", action="store_true",
+                   help="--input_sequence: stabilise every predicted pass against the stabilised previous frame, fetched along the frame's Motion Vector "
+                        "pass, before Combined is formed and the files are written; one line per frame and temporal.json at the end")
+    p.add_argument("--temporal_alpha", type=float, default=None, help="--temporal: weight of the clamped history in a blended pixel, 0 .. 1 (default 0.8: a "
+                                                                      "choice, not a measured optimum)")
+    p.add_argument("--temporal_gamma", type=float, default=None, help="--temporal: the history is clamped to mean +- gamma standard deviations of the current "
+                                                                      "frame's 3 x 3 neighbourhood (default 1.0: a choice, not a measured optimum)")
+    p.add_argument("--motion_scale", type=float, nargs=2, default=None, metavar=("SX", "SY"),
+                   help="--temporal: previous position = (x + SX * motion X, y + SY * motion Y) (default -1 1: an unverified reading of Cycles' Vector pass)")
+    p.add_argument("--temporal_guide", action="append", default=None, metavar="Pass:tolerance",
+                   help="--temporal: do not blend a pixel whose <Pass> differs from the previous frame's at the pixel it came from by more than the "
+                        "tolerance (repeatable, at most 4), e.g. Normal:0.25")
     p.add_argument("--tile_size", default=128, help="Width and heights of the tiles into which the image is split before denoising.")
     p.add_argument("--tile_overlap_size", default=14, help="Border size of the tiles that is overlapping to avoid artifacts.")
     p.add_argument("--threads", default=multiprocessing.cpu_count() + 1, help="Number of threads to use.")
@@ -94,42 +111,156 @@ def report_nonfinite(source, directory, write_png):
             print(path)
 
 
-def main(args):
-    aj = json.load(open(args.json_filename))
-    assert os.path.isdir(args.input)
-    arch = Architecture(aj, source_data_format="channels_last", data_format=args.data_format, device="cuda", dtype=args.dtype)
-    feats = openexr.load_frame(args.input, arch, device=arch.device if args.exr_decode == "device" else None, inflate=args.exr_inflate)      # Prediction.py:223-252
+TEMPORAL_OPTIONS = ("temporal_alpha", "temporal_gamma", "motion_scale", "temporal_guide")
+
+
+def check_option_rules(args):
+    """The rules across options that the parser does not know (tests parse ["a.json"] alone): -> the text of the usage error, or None."""
+    sequence = getattr(args, "input_sequence", None)
+    if (args.input is None) == (sequence is None):
+        return "exactly one of --input / --input_sequence must be given"
+    temporal_options = [o for o in TEMPORAL_OPTIONS if getattr(args, o, None) is not None]
+    if (getattr(args, "temporal", False) or temporal_options) and sequence is None:
+        return "--temporal and its options need --input_sequence"
+    if temporal_options and not getattr(args, "temporal", False):
+        return "%s need%s --temporal" % (", ".join("--" + o for o in temporal_options), "s" if len(temporal_options) == 1 else "")
+    if args.target and sequence is not None:
+        return "--target needs --input (scoring sequences is out of scope)"
+    return None
+
+
+class Run:
+    """What the frames of one process share: the architecture, the Predictor (plan, program and graph per frame size) and the loaded weights."""
+
+    def __init__(self, args):
+        self.args = args
+        self.aj = json.load(open(args.json_filename))
+        self.arch = Architecture(self.aj, source_data_format="channels_last", data_format=args.data_format, device="cuda", dtype=args.dtype)
+        self.predictor = Predictor(self.arch, tile_size=int(args.tile_size), tile_overlap_size=int(args.tile_overlap_size),
+                                   tiles_per_batch=args.tiles_per_batch, nonfinite=args.nonfinite, tile_blend=args.tile_blend, blend_width=args.blend_width)
+        self.loaded = False
+
+    def load_weights(self):
+        if self.loaded:
+            return
+        directory = os.path.dirname(os.path.abspath(self.args.json_filename))
+        model_dir = self.aj["model_directory"] if os.path.isabs(self.aj["model_directory"]) else os.path.join(directory, self.aj["model_directory"])
+        latest = tf_checkpoint.latest_checkpoint(model_dir) if os.path.isdir(model_dir) else None
+        if latest is None:
+            raise SystemExit("no checkpoint in %s (train first: python -m deepdenoiser_amd.train ...)" % model_dir)
+        tf_checkpoint.load_variables(self.arch, latest, load_optimizer=False)      # Prediction.py:497-505 restores the Estimator's latest checkpoint
+        self.loaded = True
+
+
+def load_passes(directory, names, args, device):
+    """--temporal: the [H,W,3] device tensors of the passes `names` of a frame directory, by the '_<Pass>_' file rule, decoded where --exr_decode
+    says.  A frame without one of them is an ExrError that names the directory."""
+    frame = openexr.OpenEXRDirectory(directory)
+    paths = [frame.file_of(name) for name in names]
+    if args.exr_decode == "device":
+        decoded = openexr.DeviceDecoder(device, inflate=args.exr_inflate).decode([(path, 3) for path in paths])
+        return {name: image for name, (image, _) in zip(names, decoded)}
+    return {name: torch.from_numpy(np.ascontiguousarray(openexr.read_image(path))).to(device) for name, path in zip(names, paths)}
+
+
+def stabilise(run, stabilizer, directory, out):
+    """--temporal: the predicted passes of `out` through the stabiliser, then Combined and the four combined features from the STABILISED
+    members (prediction.recombine), so that what is written stays consistent with its parts.  -> the dictionary to write, in out's order."""
+    from .naming import Naming
+    from .prediction import RECOMBINE_MEMBERS, recombine
+    arch, args = run.arch, run.args
+    guide_names = [g for g, _ in stabilizer.guides]
+    passes = load_passes(directory, ["Motion Vector"] + guide_names, args, arch.device)
+    members = [Naming.feature_prediction_name(f.name) for f in arch.feature_predictions if f.is_target and f.load_data]
+    stable = stabilizer.stabilize({k: out[k] for k in members}, passes["Motion Vector"], {g: passes[g] for g in guide_names})
+    result = dict(stable)
+    if all(Naming.feature_prediction_name(m) in stable for m in RECOMBINE_MEMBERS):
+        first = stable[members[0]]
+        result.update(recombine(run.predictor.lib, {m: stable[Naming.feature_prediction_name(m)] for m in RECOMBINE_MEMBERS},
+                                first.shape[0] * first.shape[1], torch.cuda.current_stream().cuda_stream))
+    return {k: result[k] for k in out}
+
+
+def denoise_frame(run, directory, stabilizer=None):
+    """One frame directory: its .exr files -> the prediction -> <Pass>.npy (and what the options add) next to the inputs.  -> the stabiliser's
+    report of the frame, or None."""
+    args, arch, predictor = run.args, run.arch, run.predictor
+    feats = openexr.load_frame(directory, arch, device=arch.device if args.exr_decode == "device" else None, inflate=args.exr_inflate)      # Prediction.py:223-252
     first = next(iter(feats.values()))
     height, width = first.shape[0], first.shape[1]
     mode = args.nonfinite
-    predictor = Predictor(arch, tile_size=int(args.tile_size), tile_overlap_size=int(args.tile_overlap_size), tiles_per_batch=args.tiles_per_batch,
-                          nonfinite=mode, tile_blend=args.tile_blend, blend_width=args.blend_width)
     predictor.prepare(height, width)                                               # raises for frames smaller than 16 pixels (Prediction.py:259-261)
-    directory = os.path.dirname(os.path.abspath(args.json_filename))
-    model_dir = aj["model_directory"] if os.path.isabs(aj["model_directory"]) else os.path.join(directory, aj["model_directory"])
-    latest = tf_checkpoint.latest_checkpoint(model_dir) if os.path.isdir(model_dir) else None
-    if latest is None:
-        raise SystemExit("no checkpoint in %s (train first: python -m deepdenoiser_amd.train ...)" % model_dir)
-    tf_checkpoint.load_variables(arch, latest, load_optimizer=False)               # Prediction.py:497-505 restores the Estimator's latest checkpoint
+    run.load_weights()
     frame = {k: v if torch.is_tensor(v) else torch.from_numpy(np.ascontiguousarray(v)) for k, v in feats.items()}
     try:
         out = predictor.predict_frame(frame)
     except ValueError:
         if mode != "error" or predictor._scanner is None:
             raise
-        report_nonfinite(predictor, args.input, args.nonfinite_png)
+        report_nonfinite(predictor, directory, args.nonfinite_png)
         raise SystemExit("non-finite values in the input passes (--nonfinite repair denoises the frame anyway)")
     if mode == "repair":
-        report_nonfinite(predictor, args.input, args.nonfinite_png)
+        report_nonfinite(predictor, directory, args.nonfinite_png)
     elif args.nonfinite_png:      # "keep": the prediction is today's; the frame is scanned for the pictures alone
         scanner = Scanner(arch.device, [(k, tuple(v.shape)) for k, v in frame.items()])
         scanner.scan({k: v.to(arch.device) for k, v in frame.items()})
-        report_nonfinite(scanner, args.input, True)
-    for path in openexr.save_predictions(args.input, out, as_exr=args.exr, encode=args.exr_encode, pixel_type=args.exr_type, png=args.png,
+        report_nonfinite(scanner, directory, True)
+    report = None
+    if stabilizer is not None:
+        out = stabilise(run, stabilizer, directory, out)
+        report = stabilizer.report()
+    for path in openexr.save_predictions(directory, out, as_exr=args.exr, encode=args.exr_encode, pixel_type=args.exr_type, png=args.png,
                                          png_encode=args.png_encode, exposure=args.exposure):        # Prediction.py:483-510
         print(path)
     if args.target:
         report_quality(args, arch, out)
+    return report
+
+
+def temporal_line(directory, report):
+    """One line per frame of a --temporal run: the pixels blended of the first pass's categories and the flicker over all passes."""
+    first = next(iter(report.values()))
+    pixels = sum(first[k] for k in ("pixels_offscreen", "pixels_guide", "pixels_nonfinite", "pixels_blended"))
+    before = [r["flicker_before"] for r in report.values() if r["flicker_before"] is not None]
+    after = [r["flicker_after"] for r in report.values() if r["flicker_after"] is not None]
+    if not before:
+        return "%s: passed through (the first frame of the history)" % directory
+    return ("%s: %d of %d pixels blended, %d offscreen, %d rejected by a guide, %d non-finite (%s); mean |frame - history| %.6g -> %.6g over %d passes"
+            % (directory, first["pixels_blended"], pixels, first["pixels_offscreen"], first["pixels_guide"], first["pixels_nonfinite"],
+               next(iter(report)), sum(before) / len(before), sum(after) / len(after), len(before)))
+
+
+def main(args):
+    message = check_option_rules(args)
+    if message:
+        raise SystemExit(message)
+    if args.input is not None:
+        assert os.path.isdir(args.input)
+        denoise_frame(Run(args), args.input)
+        return
+    from . import temporal
+    assert os.path.isdir(args.input_sequence)
+    directories = temporal.frame_directories(args.input_sequence)
+    if not directories:
+        raise SystemExit("no sub-directory of %s holds .exr files" % args.input_sequence)
+    stabilizer = None
+    if args.temporal:
+        try:
+            guides = [temporal.parse_guide(g) for g in (args.temporal_guide or [])]
+            stabilizer = temporal.TemporalStabilizer("cuda", alpha=0.8 if args.temporal_alpha is None else args.temporal_alpha,
+                                                     gamma=1.0 if args.temporal_gamma is None else args.temporal_gamma,
+                                                     motion_scale=args.motion_scale or (-1.0, 1.0), guides=guides)
+        except ValueError as e:
+            raise SystemExit("--temporal: %s" % e)
+    run = Run(args)
+    reports = [(d, denoise_frame(run, d, stabilizer)) for d in directories]
+    if stabilizer is not None:
+        for d, report in reports:
+            print(temporal_line(d, report))
+        path = os.path.join(args.input_sequence, "temporal.json")
+        with open(path, "w") as f:
+            json.dump(dict(stabilizer.parameters(), frames=[{"directory": os.path.basename(d), "passes": report} for d, report in reports]), f, indent=1)
+        print(path)
 
 
 if __name__ == "__main__":

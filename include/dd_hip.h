@@ -729,6 +729,52 @@ long dd_frame_quality_scratch_bytes(int n_pairs, int H, int W);
 int dd_frame_quality(const dd_quality_pair* pairs, int n_pairs, int H, int W, const float* thresholds, float exposure, float epsilon,
                      float* const* ssim_maps, void* records, void* scratch, dd_stream stream);
 
+/* ---- temporal stabilisation of a denoised frame sequence (csrc/dd_temporal.hip).  The reference has no such step (Prediction.py denoises
+ * every frame on its own); it stands behind predict's --temporal.  Up to DD_TEMPORAL_MAX_PASSES passes of one frame size in ONE call: one
+ * stabilising launch over all passes and one launch that adds the workgroups' partial records up.  A pass: `current` (the frame just denoised),
+ * `history` (the stabilised previous frame) and `out`, fp32 images [H,W,ld] of which the first nch (1 or 3) channels are used, ld >= nch each
+ * (a 1-channel prediction is a [..., :1] view of a 3-wide frame: ld 3, nch 1).  motion: fp32 [H,W,motion_ld], channels 0 and 1 used.  A
+ * guide: `current` and `previous` of the same form and a tolerance.  passes and guides are HOST arrays (copied by value).
+ * Per pixel (x = column, y = row), decided ONCE and shared by all passes, in fp32 with one rounding per operation:
+ *   px = x + sx * motion[y,x,0], py = y + sy * motion[y,x,1]: where the pixel was in the previous frame
+ *   offscreen    : px or py not finite or outside [0, W-1] x [0, H-1]
+ *   taps         : x0 = floor(px), fx = px - x0, y0 = floor(py), fy = py - y0; (y0,x0) (y0,x0+1) (y0+1,x0) (y0+1,x0+1), indices clamped
+ *   guide        : for ANY guide, |current[y,x,c] - previous[floor(py + 0.5), floor(px + 0.5), c]| (indices clamped) is not <= tolerance for
+ *                  some channel c (a non-finite difference rejects).  offscreen takes precedence over guide.
+ * Per pass and pixel:
+ *   h            : (t00 (1-fx) + t01 fx)(1-fy) + (t10 (1-fx) + t11 fx) fy of `history`
+ *   per channel  : the 3 x 3 window of `current` around the pixel (coordinates clamped at the border), its mean m (the nine values added in
+ *                  row-major order, times 1/9) and population standard deviation s = sqrt(E[v^2] - m^2), taken as sqrt(mean((v - m)^2));
+ *                  lo = m - gamma s, hi = m + gamma s, hc = min(max(h, lo), hi)
+ *   nonfinite    : any used channel of h or of the nine window values is not finite
+ *   out          : `current` bit for bit (NaN payloads included) where the pixel is offscreen, guide-rejected or nonfinite; every other pixel
+ *                  is BLENDED: current + alpha * (hc - current).  Every used channel of every pixel of out is written exactly once; channels
+ *                  nch .. ld-1 are not touched.
+ * A RECORD per pass (DEVICE, 64 bytes, 8-byte aligned, overwritten):
+ *   uint64 pixels_offscreen, pixels_guide, pixels_nonfinite, pixels_blended     exact; they add up to H * W
+ *   uint64 values_clamped                  channels of blended pixels with h < lo or h > hi
+ *   double change, flicker_before, flicker_after     sums over blended pixels and channels of the fp32 terms |out - current| | |current - h| |
+ *                                          |out - h|, added in double in a fixed order across a workgroup and across workgroups (no
+ *                                          floating-point atomics)
+ * Two runs give the same bits, and a pass's record and output depend neither on its index nor on the other passes of the call.  A workgroup
+ * owns DD_TEMPORAL_TILE^2 pixels.  scratch: >= dd_temporal_scratch_bytes (negative for a bad shape), 8-byte aligned; a shorter one cannot be
+ * detected.  Refused with a negative status before any launch: n_passes outside 1 .. 32, n_guides outside 0 .. 4, nch outside {1, 3}, an
+ * ld < nch, motion_ld < 2, H or W < 1, alpha outside [0, 1], gamma < 0, a negative tolerance or a non-finite parameter, a NULL pointer, and
+ * an `out` that is `current` or `history` of any pass of the call (neighbours read both, so in place is not possible).  No host sync. */
+#define DD_TEMPORAL_MAX_PASSES 32
+#define DD_TEMPORAL_MAX_GUIDES 4
+#define DD_TEMPORAL_TILE 16
+typedef struct { const float* current; const float* history; float* out; int current_ld, history_ld, out_ld, nch; } dd_temporal_pass;
+typedef struct { const float* current; const float* previous; int current_ld, previous_ld, nch; float tolerance; } dd_temporal_guide;
+typedef struct {
+  uint64_t pixels_offscreen, pixels_guide, pixels_nonfinite, pixels_blended, values_clamped;
+  double change, flicker_before, flicker_after;
+} dd_temporal_record;
+long dd_temporal_scratch_bytes(int n_passes, int H, int W);
+int dd_temporal_stabilize(const dd_temporal_pass* passes, int n_passes, const dd_temporal_guide* guides, int n_guides, int H, int W,
+                          const float* motion, int motion_ld, float sx, float sy, float alpha, float gamma, void* records, void* scratch,
+                          dd_stream stream);
+
 /* ---- small helpers of the graph executor */
 /* dst (+)= src * (mask > 0)   (identity/residual gradient paths into ReLU outputs); mask may be NULL; dst == src is allowed.
  * dd_masked_add, dd_zero_stuff, dd_zero_unstuff and dd_space_to_depth2 move 4 elements at a time: C (cp) and every ld multiples of 4, every
