@@ -991,6 +991,13 @@ template <typename T>
 static int kpcn_dispatch(bool fwd, const float* src, int ldsrc, const void* logits, int ldl, const float* dout, int lddo,
                          void* out, int ldo, int pad, int B, int H, int W, int ks, hipStream_t s,
                          const void* hid = nullptr, int kh = 0, const float* wb = nullptr, int ldw = 0, const float* bb = nullptr) {
+  // every entry passes through here and nothing below launches before these hold
+  DD_REQUIRE(ks == 3 || ks == 5 || ks == 7, "kernel prediction: kernel_size %d unsupported (3, 5, 7)", ks);
+  DD_REQUIRE(B > 0 && H > 0 && W > 0 && ldsrc >= 3 && ldo >= (fwd ? 3 : ks * ks) && (fwd || (lddo >= 3 && pad >= ks * ks)),
+             "dd_kpcn: bad shape (B, H, W > 0; src, out and dout rows of at least 3 channels; dl_pad and lddl at least k*k)");
+  // sym_index mirrors once: a tap further out than the image is wide would be read outside it (TensorFlow's SYMMETRIC pad refuses these shapes too)
+  DD_REQUIRE(H >= (ks - 1) / 2 && W >= (ks - 1) / 2, "dd_kpcn: image smaller than the symmetric pad");
+  DD_REQUIRE((long)B * H * W < (1L << 31), "dd_kpcn: B*H*W must stay below 2^31");
   const long total = (long)B * H * W;
   const dim3 g(grid_for(total, 128)), blk(128);
   // 16-byte vector path: the logits (and, backward, the logit gradients) of this call start 16-byte aligned and are padded to whole vectors
@@ -1009,7 +1016,7 @@ static int kpcn_dispatch(bool fwd, const float* src, int ldsrc, const void* logi
     break;
   switch (ks) {
     KP_CASE(3) KP_CASE(5) KP_CASE(7)
-    default: dd_set_error("kernel prediction: kernel_size %d unsupported (3, 5, 7)", ks); return DD_ERR_INVALID;
+    default: return DD_ERR_INVALID;      // (refused above)
   }
 #undef KP_CASE
 #undef KP_LAUNCH
@@ -1018,12 +1025,14 @@ static int kpcn_dispatch(bool fwd, const float* src, int ldsrc, const void* logi
 }
 extern "C" int dd_kpcn_fwd(const float* src, int ldsrc, const void* logits, int ldl, float* out, int ldo,
                            int B, int H, int W, int ksize, int dtype, dd_stream stream) {
+  DD_REQUIRE(dd_dtype_ok(dtype), "dd_kpcn_fwd: bad dtype %d", dtype);
   DD_REQUIRE(src && logits && out && ldl >= ksize * ksize, "dd_kpcn_fwd: bad arguments");
   DD_DISPATCH_DTYPE(dtype, T, return kpcn_dispatch<T>(true, src, ldsrc, logits, ldl, nullptr, 0, out, ldo, 0, B, H, W, ksize, S(stream)));
   return DD_ERR_INVALID;
 }
 extern "C" int dd_kpcn_bwd(const float* src, int ldsrc, const void* logits, int ldl, const float* dout, int lddo,
                            void* dlogits, int lddl, int dl_pad, int B, int H, int W, int ksize, int dtype, dd_stream stream) {
+  DD_REQUIRE(dd_dtype_ok(dtype), "dd_kpcn_bwd: bad dtype %d", dtype);
   DD_REQUIRE(src && logits && dout && dlogits && ldl >= ksize * ksize && dl_pad <= lddl, "dd_kpcn_bwd: bad arguments");
   DD_DISPATCH_DTYPE(dtype, T, return kpcn_dispatch<T>(false, src, ldsrc, logits, ldl, dout, lddo, dlogits, lddl, dl_pad, B, H, W, ksize, S(stream)));
   return DD_ERR_INVALID;
@@ -1034,12 +1043,14 @@ static bool kpcn_hidden_ok(const void* hid, int ldh, int kh, const float* wb, in
 }
 extern "C" int dd_kpcn_hidden_fwd(const float* src, int ldsrc, const void* hid, int ldh, int kh, const float* wb, int ldw, const float* bb,
                                   float* out, int ldo, int B, int H, int W, int ksize, int dtype, dd_stream stream) {
+  DD_REQUIRE(dd_dtype_ok(dtype), "dd_kpcn_hidden_fwd: bad dtype %d", dtype);
   DD_REQUIRE(src && out && kpcn_hidden_ok(hid, ldh, kh, wb, ldw, bb, ksize, dtype), "dd_kpcn_hidden_fwd: bad arguments (hid rows must be 16-byte vectors, ldw >= k*k)");
   DD_DISPATCH_DTYPE(dtype, T, return kpcn_dispatch<T>(true, src, ldsrc, nullptr, ldh, nullptr, 0, out, ldo, 0, B, H, W, ksize, S(stream), hid, kh, wb, ldw, bb));
   return DD_ERR_INVALID;
 }
 extern "C" int dd_kpcn_hidden_bwd(const float* src, int ldsrc, const void* hid, int ldh, int kh, const float* wb, int ldw, const float* bb,
                                   const float* dout, int lddo, void* dlogits, int lddl, int dl_pad, int B, int H, int W, int ksize, int dtype, dd_stream stream) {
+  DD_REQUIRE(dd_dtype_ok(dtype), "dd_kpcn_hidden_bwd: bad dtype %d", dtype);
   DD_REQUIRE(src && dout && dlogits && dl_pad <= lddl && kpcn_hidden_ok(hid, ldh, kh, wb, ldw, bb, ksize, dtype), "dd_kpcn_hidden_bwd: bad arguments");
   DD_DISPATCH_DTYPE(dtype, T, return kpcn_dispatch<T>(false, src, ldsrc, nullptr, ldh, dout, lddo, dlogits, lddl, dl_pad, B, H, W, ksize, S(stream), hid, kh, wb, ldw, bb));
   return DD_ERR_INVALID;

@@ -265,7 +265,12 @@ int dd_assemble_input_frames(const dd_assemble_entry* table, int n_tuples, int n
                              int B, int H, int W, int dtype, const int* origins_yx, int frame_h, int frame_w, dd_stream stream);
 
 /* ---- kernel prediction (KernelPrediction.kernel_prediction, KernelPrediction.py:11-63): softmax over k*k logits,
- * symmetric pad, per-pixel k x k filter of the 3-channel source. */
+ * symmetric pad, per-pixel k x k filter of the 3-channel source.
+ * All four entries REFUSE (DD_ERR_INVALID, dd_last_error names the reason, nothing is launched): ksize other than 3, 5, 7; a dtype that
+ * is none of DD_F32 / DD_BF16 / DD_F16; B, H or W <= 0; H or W below the pad (ksize - 1) / 2 -- the symmetric index mirrors once, so a
+ * smaller image would be read outside itself, and TensorFlow's SYMMETRIC pad rejects such shapes as well; B * H * W >= 2^31;
+ * ldsrc, ldo (and, backward, lddo) < 3; ldl (ldw) < k*k; backward: dl_pad > lddl or dl_pad < k*k (channels 0..k*k-1 of a d logits
+ * row are always written, k*k..dl_pad-1 are set to +0, anything beyond dl_pad is left alone); null pointers. */
 int dd_kpcn_fwd(const float* src, int ldsrc, const void* logits, int ldl, float* out, int ldo,
                 int B, int H, int W, int ksize, int dtype, dd_stream stream);
 int dd_kpcn_bwd(const float* src, int ldsrc, const void* logits, int ldl, const float* dout, int lddo,
