@@ -23,6 +23,7 @@ PREVIEW_MAX_IMAGES, PREVIEW_THRESHOLDS = 16, 255
 NONFINITE_MAX_PLANES = 32      # DD_NONFINITE_MAX_PLANES
 QUALITY_MAX_PAIRS, QUALITY_TILE = 32, 32      # DD_QUALITY_MAX_PAIRS, DD_QUALITY_TILE
 TEMPORAL_MAX_PASSES, TEMPORAL_MAX_GUIDES, TEMPORAL_TILE = 32, 4, 16      # DD_TEMPORAL_MAX_PASSES, DD_TEMPORAL_MAX_GUIDES, DD_TEMPORAL_TILE
+SEQQ_MAX_PAIRS, SEQQ_TILE = 32, 16      # DD_SEQQ_MAX_PAIRS, DD_SEQQ_TILE
 GRAD_CHUNK, GRAD_PARTIAL_BYTES = 4096, 24      # DD_GRAD_CHUNK, DD_GRAD_PARTIAL_BYTES
 
 
@@ -54,7 +55,7 @@ SYMBOLS = (
     "dd_grad_norms", "dd_adam_step_clipped", "dd_adam_step_scaled_clipped", "dd_sample_tiles",
     "dd_tile_statistics", "dd_importance_cells", "dd_importance_update", "dd_exr_reconstruct", "dd_exr_inflate",
     "dd_exr_pack", "dd_exr_deflate_workspace", "dd_exr_deflate", "dd_png_pack", "dd_png_deflate_workspace", "dd_png_deflate",
-    "dd_temporal_scratch_bytes", "dd_temporal_stabilize",
+    "dd_temporal_scratch_bytes", "dd_temporal_stabilize", "dd_sequence_quality_scratch_bytes", "dd_sequence_quality",
 )
 
 
@@ -403,6 +404,17 @@ class TemporalRecord(C.Structure):      # dd_temporal_record: what dd_temporal_s
                 ("values_clamped", C.c_uint64), ("change", C.c_double), ("flicker_before", C.c_double), ("flicker_after", C.c_double)]
 
 
+class SequenceQualityPair(C.Structure):        # dd_seqq_pair (56 bytes)
+    _fields_ = [("pred", C.c_void_p), ("pred_previous", C.c_void_p), ("target", C.c_void_p), ("target_previous", C.c_void_p), ("pred_ld", C.c_int),
+                ("pred_previous_ld", C.c_int), ("target_ld", C.c_int), ("target_previous_ld", C.c_int), ("nch", C.c_int)]
+
+
+class SequenceQualityRecord(C.Structure):      # dd_seqq_record: what dd_sequence_quality leaves per pair in device memory (72 bytes)
+    _fields_ = [("pixels_offscreen", C.c_uint64), ("pixels_nonfinite", C.c_uint64), ("pixels_valid", C.c_uint64), ("change_prediction", C.c_double),
+                ("change_target", C.c_double), ("temporal_error", C.c_double), ("ldr_change_prediction", C.c_double), ("ldr_change_target", C.c_double),
+                ("ldr_temporal_error", C.c_double)]
+
+
 _lib = None
 
 
@@ -554,6 +566,9 @@ def load():
     lib.dd_temporal_scratch_bytes.argtypes = [i, i, i]
     lib.dd_temporal_scratch_bytes.restype = l
     lib.dd_temporal_stabilize.argtypes = [C.POINTER(TemporalPass), i, C.POINTER(TemporalGuide), i, i, i, vp, i, f, f, f, f, vp, vp, vp]
+    lib.dd_sequence_quality_scratch_bytes.argtypes = [i, i, i]
+    lib.dd_sequence_quality_scratch_bytes.restype = l
+    lib.dd_sequence_quality.argtypes = [C.POINTER(SequenceQualityPair), i, i, i, vp, i, f, f, vp, f, vp, vp, vp]
     _lib = lib
     return lib
 

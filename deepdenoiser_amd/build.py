@@ -17,9 +17,9 @@ SOURCES = ["dd_conv_igemm.hip", "dd_conv_wgrad.hip", "dd_pointwise.hip", "dd_com
            "dd_conv_rw.hip", "dd_conv_ks.hip", "dd_conv_pw.hip", "dd_conv_bwd96.hip", "dd_compose_stream.hip", "dd_compose_stream_bwd.hip", "dd_loss_msssim.hip",
            "dd_metrics.hip", "dd_loss_scale.hip", "dd_histogram.hip", "dd_preview.hip", "dd_nonfinite.hip", "dd_quality.hip", "dd_grad_norm.hip", "dd_tile_sampler.hip",
            "dd_frame_statistics.hip", "dd_frame_importance.hip", "dd_importance_update.hip", "dd_exr_decode.hip", "dd_exr_inflate.hip",
-           "dd_exr_encode.hip", "dd_exr_deflate.hip", "dd_png_encode.hip", "dd_temporal.hip"]
+           "dd_exr_encode.hip", "dd_exr_deflate.hip", "dd_png_encode.hip", "dd_temporal.hip", "dd_sequence_quality.hip"]
 VERSION_SRC = "dd_version.hip"
-HEADERS = ["dd_common.h", "dd_compose_stream.h", "dd_loss_common.h", "dd_metrics_stage.h", "dd_inflate_core.h", "dd_deflate_core.h", "dd_png_core.h", os.path.join("..", "..", "include", "dd_hip.h")]
+HEADERS = ["dd_common.h", "dd_compose_stream.h", "dd_loss_common.h", "dd_metrics_stage.h", "dd_inflate_core.h", "dd_deflate_core.h", "dd_png_core.h", "dd_motion.h", os.path.join("..", "..", "include", "dd_hip.h")]
 LIB = os.path.join(HERE, "libdd_hip.so")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function"]
 # Kernels that must not use scratch memory.  (1) Kernels whose long-lived accumulators are updated by in-place inline-asm MFMAs (no hazard
@@ -55,6 +55,7 @@ NO_SCRATCH = {
     "dd_exr_deflate.hip": ("exr_deflate_kernel",),
     "dd_png_encode.hip": ("png_pack_kernel", "png_deflate_kernel"),
     "dd_temporal.hip": ("temporal_stabilize_kernel", "temporal_finalize_kernel"),
+    "dd_sequence_quality.hip": ("sequence_quality_kernel", "sequence_quality_finalize_kernel"),
 }
 
 

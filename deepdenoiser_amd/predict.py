@@ -2,7 +2,9 @@
 --input dir` (TensorFlow/Prediction.py:23-53 argument set, :188-520 main): the directory's per-pass .exr files -> halo tiles -> forward on the
 MI355X path (fp16 MFMA by default) -> crop / stitch / recombination -> <Pass>.npy and Combined.npy next to the inputs.
 `--input_sequence <parent directory>` denoises every frame directory below it in one process with one Predictor; `--temporal` stabilises the
-predicted passes of each frame against the previous one before the recombination (temporal.py, DESIGN 3.31: the reference has no such step)."""
+predicted passes of each frame against the previous one before the recombination (temporal.py, DESIGN 3.31: the reference has no such step);
+`--target_sequence <parent directory>` scores every written frame against the target frame of its name and the sequence against its targets'
+change from frame to frame (sequence_quality.py)."""
 import argparse
 import json
 import multiprocessing
@@ -33,7 +35,8 @@ def parser():
     p.add_argument("--temporal_gamma", type=float, default=None, help="--temporal: the history is clamped to mean +- gamma standard deviations of the current "
                                                                       "frame's 3 x 3 neighbourhood (default 1.0: a choice, not a measured optimum)")
     p.add_argument("--motion_scale", type=float, nargs=2, default=None, metavar=("SX", "SY"),
-                   help="--temporal: previous position = (x + SX * motion X, y + SY * motion Y) (default -1 1: an unverified reading of Cycles' Vector pass)")
+                   help="--temporal, --target_sequence: previous position = (x + SX * motion X, y + SY * motion Y) (default -1 1: an unverified reading "
+                        "of Cycles' Vector pass)")
     p.add_argument("--temporal_guide", action="append", default=None, metavar="Pass:tolerance",
                    help="--temporal: do not blend a pixel whose <Pass> differs from the previous frame's at the pixel it came from by more than the "
                         "tolerance (repeatable, at most 4), e.g. Normal:0.25")
@@ -68,14 +71,27 @@ def parser():
                         "computed on exactly those pictures)")
     p.add_argument("--quality_json", type=str, default=None, help="--target: where to write the figures (default: quality.json next to the inputs)")
     p.add_argument("--ssim_png", action="store_true", help="--target: write <Pass>_ssim.png, the SSIM map (gray; magenta: a window with a NaN / Inf pixel)")
+    p.add_argument("--target_sequence", type=str, default=None,
+                   help="--input_sequence: the directory with the ground-truth renders of the sequence, one sub-directory per frame named as the input "
+                        "frame's.  Every frame is scored as --target scores it (the table and quality.json in the frame directory; --exposure and "
+                        "--ssim_png apply), and from the second frame on against its previous frame along the frame's Motion Vector pass: how much "
+                        "the error changes from frame to frame (on what is written: the stabilised passes with --temporal).  One line per pass and "
+                        "sequence_quality.json at the end")
+    p.add_argument("--sequence_quality_json", type=str, default=None,
+                   help="--target_sequence: where to write the figures of the sequence (default: sequence_quality.json in the --input_sequence directory)")
     return p
 
 
-def report_quality(args, arch, out):
-    """--target: the predictions `out` (still on the device) against the target frame: one dd_frame_quality call, one copy of the records."""
+def report_quality(args, arch, out, directory=None, targets=None, json_path=None, scorer=None):
+    """--target: the predictions `out` (still on the device) against the target frame: one dd_frame_quality call, one copy of the records.
+    directory: where the pictures and quality.json go (default: --input); targets: the loaded target frame (default: --target's); json_path: of the
+    json (default: --quality_json, else quality.json in the directory); scorer: a FrameQuality to reuse.  -> the figures."""
     from . import quality      # (imported here: a run without --target does not load it)
-    targets = quality.targets_of_frame(args.target, arch, device=arch.device)
-    result = quality.FrameQuality(arch.device, exposure=args.exposure).measure(out, targets, ssim_maps=args.ssim_png)
+    directory = args.input if directory is None else directory
+    if targets is None:
+        targets = quality.targets_of_frame(args.target, arch, device=arch.device)
+    scorer = scorer or quality.FrameQuality(arch.device, exposure=args.exposure)
+    result = scorer.measure(out, targets, ssim_maps=args.ssim_png)
     maps = {}
     if args.ssim_png:
         result, maps = result
@@ -83,16 +99,17 @@ def report_quality(args, arch, out):
     for line in quality.table_lines(short):
         print(line)
     for key, ssim_map in maps.items():
-        path = os.path.join(args.input, (key.split("/", 1)[1] if key.startswith("prediction/") else key) + "_ssim.png")
+        path = os.path.join(directory, (key.split("/", 1)[1] if key.startswith("prediction/") else key) + "_ssim.png")
         with open(path, "wb") as f:
             f.write(encode_png(quality.ssim_picture(ssim_map)))
         print(path)
-    path = args.quality_json or os.path.join(args.input, "quality.json")
+    path = json_path or args.quality_json or os.path.join(directory, "quality.json")
     document = {"tile_size": int(args.tile_size), "tile_overlap_size": int(args.tile_overlap_size), "dtype": args.dtype, "nonfinite": args.nonfinite,
                 "tile_blend": args.tile_blend, "exposure": float(args.exposure), "quality": result}
     with open(path, "w") as f:
         json.dump(document, f, indent=1)
     print(path)
+    return result
 
 
 def report_nonfinite(source, directory, write_png):
@@ -119,9 +136,14 @@ def check_option_rules(args):
     sequence = getattr(args, "input_sequence", None)
     if (args.input is None) == (sequence is None):
         return "exactly one of --input / --input_sequence must be given"
+    target_sequence = getattr(args, "target_sequence", None)
+    if target_sequence is not None and sequence is None:
+        return "--target_sequence needs --input_sequence"
     temporal_options = [o for o in TEMPORAL_OPTIONS if getattr(args, o, None) is not None]
     if (getattr(args, "temporal", False) or temporal_options) and sequence is None:
         return "--temporal and its options need --input_sequence"
+    if target_sequence is not None and not getattr(args, "temporal", False):      # (the scorer follows the motion vectors too)
+        temporal_options = [o for o in temporal_options if o != "motion_scale"]
     if temporal_options and not getattr(args, "temporal", False):
         return "%s need%s --temporal" % (", ".join("--" + o for o in temporal_options), "s" if len(temporal_options) == 1 else "")
     if args.target and sequence is not None:
@@ -153,8 +175,8 @@ class Run:
 
 
 def load_passes(directory, names, args, device):
-    """--temporal: the [H,W,3] device tensors of the passes `names` of a frame directory, by the '_<Pass>_' file rule, decoded where --exr_decode
-    says.  A frame without one of them is an ExrError that names the directory."""
+    """--temporal, --target_sequence: the [H,W,3] device tensors of the passes `names` of a frame directory, by the '_<Pass>_' file rule, decoded
+    where --exr_decode says.  A frame without one of them is an ExrError that names the directory."""
     frame = openexr.OpenEXRDirectory(directory)
     paths = [frame.file_of(name) for name in names]
     if args.exr_decode == "device":
@@ -163,14 +185,14 @@ def load_passes(directory, names, args, device):
     return {name: torch.from_numpy(np.ascontiguousarray(openexr.read_image(path))).to(device) for name, path in zip(names, paths)}
 
 
-def stabilise(run, stabilizer, directory, out):
+def stabilise(run, stabilizer, passes, out):
     """--temporal: the predicted passes of `out` through the stabiliser, then Combined and the four combined features from the STABILISED
-    members (prediction.recombine), so that what is written stays consistent with its parts.  -> the dictionary to write, in out's order."""
+    members (prediction.recombine), so that what is written stays consistent with its parts.  passes: the frame's Motion Vector and guide
+    passes (load_passes).  -> the dictionary to write, in out's order."""
     from .naming import Naming
     from .prediction import RECOMBINE_MEMBERS, recombine
-    arch, args = run.arch, run.args
+    arch = run.arch
     guide_names = [g for g, _ in stabilizer.guides]
-    passes = load_passes(directory, ["Motion Vector"] + guide_names, args, arch.device)
     members = [Naming.feature_prediction_name(f.name) for f in arch.feature_predictions if f.is_target and f.load_data]
     stable = stabilizer.stabilize({k: out[k] for k in members}, passes["Motion Vector"], {g: passes[g] for g in guide_names})
     result = dict(stable)
@@ -181,9 +203,51 @@ def stabilise(run, stabilizer, directory, out):
     return {k: result[k] for k in out}
 
 
-def denoise_frame(run, directory, stabilizer=None):
-    """One frame directory: its .exr files -> the prediction -> <Pass>.npy (and what the options add) next to the inputs.  -> the stabiliser's
-    report of the frame, or None."""
+class SequenceScore:
+    """--target_sequence: what the frames of the run share (the two scorers) and what they leave (the figures per frame)."""
+
+    def __init__(self, args, device):
+        from . import quality, sequence_quality
+        self.parent = args.target_sequence
+        self.frame_quality = quality.FrameQuality(device, exposure=args.exposure)
+        self.sequence_quality = sequence_quality.SequenceQuality(device, exposure=args.exposure, motion_scale=args.motion_scale or (-1.0, 1.0))
+        self.frames = []
+
+    @staticmethod
+    def check_directories(parent, directories):
+        """Every frame directory needs a sub-directory of its name under `parent` with .exr files: -> the first one that is missing, or None."""
+        for d in directories:
+            t = os.path.join(parent, os.path.basename(d))
+            if not (os.path.isdir(t) and any(n.endswith(".exr") for n in os.listdir(t))):
+                return t
+        return None
+
+    def score(self, run, directory, out, motion):
+        """The frame as --target scores it (into the frame directory), then against the previous frame along `motion`."""
+        from . import quality
+        args, arch = run.args, run.arch
+        targets = quality.targets_of_frame(os.path.join(self.parent, os.path.basename(directory)), arch, device=arch.device)
+        result = report_quality(args, arch, out, directory=directory, targets=targets, json_path=os.path.join(directory, "quality.json"), scorer=self.frame_quality)
+        temporal_quality = self.sequence_quality.measure(out, targets, motion)
+        self.frames.append({"directory": os.path.basename(directory), "quality": result, "temporal_quality": temporal_quality})
+
+    def document(self, args, stabilizer):
+        measured = self.sequence_quality.summary()
+        summary = {}
+        for name in (self.frames[0]["quality"] if self.frames else {}):
+            means = {}
+            for key in self.frames[0]["quality"][name]:
+                values = [f["quality"][name][key] for f in self.frames if f["quality"].get(name, {}).get(key) is not None]
+                means[key] = sum(values) / len(values) if values else None
+            summary[name] = {"temporal_quality": measured.get(name), "quality": means}
+        return {"exposure": float(args.exposure), "motion_scale": list(self.sequence_quality.motion_scale), "tile_size": int(args.tile_size),
+                "tile_overlap_size": int(args.tile_overlap_size), "dtype": args.dtype, "nonfinite": args.nonfinite, "tile_blend": args.tile_blend,
+                "temporal": stabilizer.parameters() if stabilizer is not None else None, "frames": self.frames, "summary": summary}
+
+
+def denoise_frame(run, directory, stabilizer=None, score=None):
+    """One frame directory: its .exr files -> the prediction -> <Pass>.npy (and what the options add) next to the inputs.  score: the
+    SequenceScore of a --target_sequence run.  -> the stabiliser's report of the frame, or None."""
     args, arch, predictor = run.args, run.arch, run.predictor
     feats = openexr.load_frame(directory, arch, device=arch.device if args.exr_decode == "device" else None, inflate=args.exr_inflate)      # Prediction.py:223-252
     first = next(iter(feats.values()))
@@ -205,15 +269,19 @@ def denoise_frame(run, directory, stabilizer=None):
         scanner = Scanner(arch.device, [(k, tuple(v.shape)) for k, v in frame.items()])
         scanner.scan({k: v.to(arch.device) for k, v in frame.items()})
         report_nonfinite(scanner, directory, True)
-    report = None
+    report, passes = None, None
+    if stabilizer is not None or score is not None:      # the Motion Vector pass of the INPUT frame, once for both
+        passes = load_passes(directory, ["Motion Vector"] + ([g for g, _ in stabilizer.guides] if stabilizer is not None else []), args, arch.device)
     if stabilizer is not None:
-        out = stabilise(run, stabilizer, directory, out)
+        out = stabilise(run, stabilizer, passes, out)
         report = stabilizer.report()
     for path in openexr.save_predictions(directory, out, as_exr=args.exr, encode=args.exr_encode, pixel_type=args.exr_type, png=args.png,
                                          png_encode=args.png_encode, exposure=args.exposure):        # Prediction.py:483-510
         print(path)
     if args.target:
         report_quality(args, arch, out)
+    if score is not None:
+        score.score(run, directory, out, passes["Motion Vector"])
     return report
 
 
@@ -243,6 +311,12 @@ def main(args):
     directories = temporal.frame_directories(args.input_sequence)
     if not directories:
         raise SystemExit("no sub-directory of %s holds .exr files" % args.input_sequence)
+    target_sequence = getattr(args, "target_sequence", None)
+    if target_sequence is not None:
+        from .sequence_quality import table_lines
+        missing = SequenceScore.check_directories(target_sequence, directories)
+        if missing:
+            raise SystemExit("--target_sequence: no target frame directory %s with .exr files" % missing)
     stabilizer = None
     if args.temporal:
         try:
@@ -253,13 +327,24 @@ def main(args):
         except ValueError as e:
             raise SystemExit("--temporal: %s" % e)
     run = Run(args)
-    reports = [(d, denoise_frame(run, d, stabilizer)) for d in directories]
+    score = SequenceScore(args, "cuda") if target_sequence is not None else None
+    reports = [(d, denoise_frame(run, d, stabilizer, score)) for d in directories]
     if stabilizer is not None:
         for d, report in reports:
             print(temporal_line(d, report))
         path = os.path.join(args.input_sequence, "temporal.json")
         with open(path, "w") as f:
             json.dump(dict(stabilizer.parameters(), frames=[{"directory": os.path.basename(d), "passes": report} for d, report in reports]), f, indent=1)
+        print(path)
+    if score is not None:
+        document = score.document(args, stabilizer)
+        measured = {(k.split("/", 1)[1] if k.startswith("prediction/") else k): v["temporal_quality"] for k, v in document["summary"].items()
+                    if v["temporal_quality"] is not None}
+        for line in table_lines(measured):
+            print(line)
+        path = args.sequence_quality_json or os.path.join(args.input_sequence, "sequence_quality.json")
+        with open(path, "w") as f:
+            json.dump(document, f, indent=1)
         print(path)
 
 

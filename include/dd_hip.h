@@ -780,6 +780,51 @@ int dd_temporal_stabilize(const dd_temporal_pass* passes, int n_passes, const dd
                           const float* motion, int motion_ld, float sx, float sy, float alpha, float gamma, void* records, void* scratch,
                           dd_stream stream);
 
+/* ---- temporal error of a denoised frame sequence against its target frames, where the frames are (csrc/dd_sequence_quality.hip).  The
+ * reference has no such measure; it stands behind predict's --target_sequence.  Up to DD_SEQQ_MAX_PAIRS pairs of one frame size in ONE call:
+ * one scoring launch over all pairs and one launch that adds the workgroups' partial records up.  A pair: `pred` and `target` (the denoised
+ * frame and its ground truth), `pred_previous` and `target_previous` (the same of the frame before), fp32 images [H,W,ld] of which the first
+ * nch (1 or 3) channels are used, every image with an ld >= nch of its own (a 1-channel pass is a [..., :1] view of a 3-wide frame: ld 3,
+ * nch 1).  motion: fp32 [H,W,motion_ld] of the CURRENT frame, channels 0 and 1 used.  pairs is a HOST array (copied by value).
+ * Per pixel (x = column, y = row), decided ONCE and shared by all pairs, in fp32 with one rounding per operation (csrc/dd_motion.h; the rules
+ * of dd_temporal_stabilize without its guides):
+ *   px = x + sx * motion[y,x,0], py = y + sy * motion[y,x,1]: where the pixel was in the previous frame
+ *   offscreen    : px or py not finite or outside [0, W-1] x [0, H-1]
+ *   taps         : x0 = floor(px), fx = px - x0, y0 = floor(py), fy = py - y0; (y0,x0) (y0,x0+1) (y0+1,x0) (y0+1,x0+1), indices clamped
+ * Per pair and pixel that is not offscreen:
+ *   nonfinite    : any of the nch channels of pred[y,x], of target[y,x] or of one of the four taps of pred_previous or target_previous is
+ *                  not finite (the bit test of dd_nonfinite_scan; a tap with weight 0 still counts).  offscreen takes precedence.
+ *   valid        : every other pixel.  Per channel, in fp32 with one rounding per operation:
+ *                  hp = (a00 (1-fx) + a01 fx)(1-fy) + (a10 (1-fx) + a11 fx) fy over the taps of pred_previous, ht the same over the taps of
+ *                  target_previous; dp = p - hp, dt = t - ht, e = dp - dt: the change of the error image E = P - T along the motion,
+ *                  E_t(x) - warp(E_t-1)(x), zero for a static bias and large for error that changes from frame to frame.
+ *                  Display-referred: the byte b(v) = the number of entries of `thresholds` <= exposure * v (one fp32 multiply; the rule and
+ *                  the table of dd_frame_quality); Hp, Ht: the same bilinear form over the bytes of the taps as floats;
+ *                  DP = b(p) - Hp, DT = b(t) - Ht, in byte units.
+ * A RECORD per pair (DEVICE, 72 bytes, 8-byte aligned, overwritten):
+ *   uint64 pixels_offscreen, pixels_nonfinite, pixels_valid      exact; they add up to H * W
+ *   double change_prediction, change_target, temporal_error      sums over valid pixels and channels of |dp| | |dt| | |e|
+ *   double ldr_change_prediction, ldr_change_target, ldr_temporal_error      the same sums of |DP| | |DT| | |DP - DT|
+ * The fp32 terms are added in double in a fixed order across a workgroup and across workgroups (no floating-point atomics): two runs give
+ * the same bits, and a pair's record depends neither on its index nor on the other pairs of the call.  A workgroup owns DD_SEQQ_TILE^2
+ * pixels.  No image is written.  scratch: >= dd_sequence_quality_scratch_bytes (negative for a bad shape), 8-byte aligned; a shorter one
+ * cannot be detected.  Refused with a negative status before any launch: n_pairs outside 1 .. 32, nch outside {1, 3}, an ld < nch,
+ * motion_ld < 2, H or W < 1, a non-finite sx, sy or exposure, a NULL or not 4-byte aligned image pointer, NULL motion, thresholds, records
+ * or scratch.  No host sync. */
+#define DD_SEQQ_MAX_PAIRS 32
+#define DD_SEQQ_TILE 16
+typedef struct {
+  const float* pred; const float* pred_previous; const float* target; const float* target_previous;
+  int pred_ld, pred_previous_ld, target_ld, target_previous_ld, nch;
+} dd_seqq_pair;
+typedef struct {
+  uint64_t pixels_offscreen, pixels_nonfinite, pixels_valid;
+  double change_prediction, change_target, temporal_error, ldr_change_prediction, ldr_change_target, ldr_temporal_error;
+} dd_seqq_record;
+long dd_sequence_quality_scratch_bytes(int n_pairs, int H, int W);
+int dd_sequence_quality(const dd_seqq_pair* pairs, int n_pairs, int H, int W, const float* motion, int motion_ld, float sx, float sy,
+                        const float* thresholds, float exposure, void* records, void* scratch, dd_stream stream);
+
 /* ---- small helpers of the graph executor */
 /* dst (+)= src * (mask > 0)   (identity/residual gradient paths into ReLU outputs); mask may be NULL; dst == src is allowed.
  * dd_masked_add, dd_zero_stuff, dd_zero_unstuff and dd_space_to_depth2 move 4 elements at a time: C (cp) and every ld multiples of 4, every
