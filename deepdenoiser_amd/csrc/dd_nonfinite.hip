@@ -6,7 +6,7 @@
 //                        a workgroup of a plane whose count is zero returns at its first branch
 // Both take the whole table in ONE launch (the plane in blockIdx.y).  Plain HBM-streaming kernels of the csrc/dd_pointwise.hip family: no LDS,
 // no inline assembly.
-#include "dd_common.h"
+#include "dd_frame_common.h"
 
 namespace {
 
@@ -17,11 +17,6 @@ constexpr int kMaxBlocksX = 1024;      // per plane; the rest is taken grid-stri
 
 // inf or NaN <=> all eight exponent bits set: the test of csrc/dd_loss_scale.hip (on the bits, nothing a fast-math build may fold away)
 __device__ __forceinline__ unsigned nonfinite_bits(unsigned u) { return (u & 0x7f800000u) == 0x7f800000u ? 1u : 0u; }
-
-__device__ __forceinline__ unsigned wave_sum(unsigned v) {
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-  return v;      // (lane 0 holds the sum)
-}
 
 // the mask byte of one pixel read value by value (any ld, any alignment)
 __device__ __forceinline__ unsigned pixel_mask(const float* __restrict__ px, int C) {

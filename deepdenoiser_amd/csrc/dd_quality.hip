@@ -4,7 +4,7 @@
 //   frame_quality_kernel   : a workgroup of 256 threads owns QT x QT pixels of one pair (blockIdx.z) and the SSIM windows whose top-left pixel
 //                            lies there, so it stages the (QT + 10)^2 patch under those windows once:
 //                            stage     every patch pixel is fetched from HBM once (12-byte loads where ld == nch == 3), tested for inf / NaN on the
-//                                      bits, quantised against the host's threshold table (the binary search of csrc/dd_preview.hip) and kept in LDS
+//                                      bits, quantised against the host's threshold table (dd_png_quantise, csrc/dd_png_core.h) and kept in LDS
 //                                      as bytes; the thread that stages an OWNED pixel adds its fp32 error terms to double accumulators
 //                            rows      the 11-tap Gaussian along x of  x, y, x^2 + y^2, x y  of the integer bytes, in double (the products are
 //                                      exact, so E[x^2] - mu^2 on a flat bright region loses nothing that a pivot would have to save), into LDS,
@@ -14,7 +14,8 @@
 //                            patch is clean.  Partial sums: a shuffle tree inside a wave, the four waves in order -> one partial record per workgroup.
 //   frame_quality_finalize_kernel : one workgroup per pair adds its partial records in a fixed order (integers exactly, the rest in double).
 // No atomics at all: two runs give the same bits; a pair's record does not depend on blockIdx.z or on its neighbours in the launch.
-#include "dd_common.h"
+#include "dd_frame_common.h"
+#include "dd_png_core.h"
 
 namespace {
 
@@ -22,11 +23,15 @@ constexpr int QT = DD_QUALITY_TILE;            // pixels (and window origins) pe
 constexpr int QP = QT + 10;                    // patch side
 constexpr int QS = 44;                         // bytes per patch row in LDS (QP rounded up to whole dwords)
 constexpr int QI = QT + 1;                     // doubles per row of the row-pass results (odd: the row-pass stores of a wave spread over the banks)
-constexpr int QTHREADS = 256;
+constexpr int QTHREADS = FRAME_THREADS;
+constexpr int QWAVES = FRAME_WAVES;
+constexpr int QU = 3, QD = 5;                  // counts and sums of a dd_quality_record (then max_abs and reserved)
 constexpr int QGROUP = 8;                      // consecutive windows of one patch row per row-pass thread
 constexpr int QTABLE = DD_PREVIEW_THRESHOLDS;
 constexpr int QITER = (QP * QP + QTHREADS - 1) / QTHREADS;      // patch pixels per thread
 static_assert(QT == 32 && QTHREADS == 8 * QT, "the column pass maps a thread to one window column and four rows");
+static_assert(frame_record_is<dd_quality_record, QU, QD, true>(offsetof(dd_quality_record, pixels_valid), offsetof(dd_quality_record, se),
+                                                               offsetof(dd_quality_record, max_abs)), "dd_quality_record: three uint64 counts, five double sums, max_abs");
 static_assert(QP * (QT / QGROUP) <= QTHREADS && QT / QGROUP * QGROUP + 12 <= QS, "one row-pass item per thread, five dwords per item");
 
 struct QualityArgs {
@@ -35,19 +40,8 @@ struct QualityArgs {
   double gauss[11];                            // normalised 1-D Gaussian, sigma 1.5 (the 2-D filter is its outer product)
 };
 
-struct __attribute__((packed, aligned(4))) Float3 { float x, y, z; };
-
-__device__ __forceinline__ bool nonfinite(float v) { return (__float_as_uint(v) & 0x7f800000u) == 0x7f800000u; }
-
-// number of table entries <= v (csrc/dd_preview.hip)
-__device__ __forceinline__ unsigned quantise(const float* thr, float v) {
-  unsigned lo = 0;
-#pragma unroll
-  for (unsigned step = 128; step > 0; step >>= 1)
-    if (thr[lo + step - 1] <= v) lo += step;
-  return lo;
-}
-
+// The pixel of a pair's image with its RUNTIME channel count (channels nch .. 2 read as 0).  Not dd_frame_common.h's load_pixel<NCH>: with the
+// template behind a branch on nch this kernel, at 146 registers, spills 192 bytes per lane (hipcc's resource report).
 __device__ __forceinline__ void load_pixel(const float* __restrict__ base, long q, int ld, int nch, float (&v)[3]) {
   v[1] = v[2] = 0.f;
   if (nch == 3 && ld == 3) {
@@ -60,19 +54,6 @@ __device__ __forceinline__ void load_pixel(const float* __restrict__ base, long 
   }
 }
 
-__device__ __forceinline__ double wave_sum(double v) {
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-  return v;
-}
-__device__ __forceinline__ unsigned wave_sum(unsigned v) {
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-  return v;
-}
-__device__ __forceinline__ float wave_max(float v) {
-  for (int off = 32; off > 0; off >>= 1) v = fmaxf(v, __shfl_down(v, off, 64));
-  return v;
-}
-
 __global__ __launch_bounds__(QTHREADS) void frame_quality_kernel(const QualityArgs a, int H, int W, const float* __restrict__ thresholds, float exposure,
                                                                  float epsilon, dd_quality_record* __restrict__ partials) {
   __shared__ float thr[QTABLE + 1];
@@ -80,9 +61,9 @@ __global__ __launch_bounds__(QTHREADS) void frame_quality_kernel(const QualityAr
   __shared__ __attribute__((aligned(16))) unsigned char invalid[QP * QS];
   __shared__ unsigned char invalid_rows[QP * QT];                                   // invalid pixels under the 11 taps along x
   __shared__ double rows[2][QP * QI];      // the row pass of two quantities at a time
-  __shared__ double wave_d[5][QTHREADS / 64];
-  __shared__ unsigned wave_u[3][QTHREADS / 64];
-  __shared__ float wave_f[QTHREADS / 64];
+  __shared__ double wave_d[QD][QWAVES];
+  __shared__ unsigned wave_u[QU][QWAVES];
+  __shared__ float wave_f[QWAVES];
 
   const int tid = threadIdx.x;
   const dd_quality_pair P = a.pair[blockIdx.z];
@@ -122,8 +103,8 @@ __global__ __launch_bounds__(QTHREADS) void frame_quality_kernel(const QualityAr
         for (int c = 0; c < 3; ++c) {
 #pragma clang fp contract(off)
           if (c >= nch) break;
-          bp[c] = quantise(thr, p[c] * exposure);
-          bt[c] = quantise(thr, t[c] * exposure);
+          bp[c] = dd_png_quantise(thr, p[c] * exposure);
+          bt[c] = dd_png_quantise(thr, t[c] * exposure);
           if (owned) {
             const float d = p[c] - t[c], ad = fabsf(d), sq = d * d;
             se += (double)sq;
@@ -261,72 +242,24 @@ __global__ __launch_bounds__(QTHREADS) void frame_quality_kernel(const QualityAr
   }
   __syncthreads();
   if (tid == 0) {
-    dd_quality_record r;
-    double d[5];
-    unsigned u[3];
-    for (int m = 0; m < 5; ++m) d[m] = ((wave_d[m][0] + wave_d[m][1]) + wave_d[m][2]) + wave_d[m][3];
-    for (int m = 0; m < 3; ++m) u[m] = wave_u[m][0] + wave_u[m][1] + wave_u[m][2] + wave_u[m][3];
-    r.pixels_valid = u[0]; r.windows_valid = u[1]; r.ldr_sq_err = u[2];
-    r.se = d[0]; r.ae = d[1]; r.rse = d[2]; r.smape = d[3]; r.ssim_sum = d[4];
-    r.max_abs = fmaxf(fmaxf(wave_f[0], wave_f[1]), fmaxf(wave_f[2], wave_f[3]));
+    FrameSums<QU, QD, true> r;
+    frame_wave_partial<QU, QD>(r.u, r.d, {wave_u[0], wave_u[1], wave_u[2]}, wave_d);
+    r.mx = fmaxf(fmaxf(wave_f[0], wave_f[1]), fmaxf(wave_f[2], wave_f[3]));
     r.reserved = 0.f;
-    partials[((long)blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x] = r;
+    reinterpret_cast<FrameSums<QU, QD, true>*>(partials)[((long)blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x] = r;
   }
 }
 
-// records[pair] = the sum of the pair's `tiles` partial records: thread t adds records t, t + 256, ... in order, then a fixed tree over the threads
+// records[pair] = the sum of the pair's `tiles` partial records (csrc/dd_frame_common.h: frame_finalize)
 __global__ __launch_bounds__(QTHREADS) void frame_quality_finalize_kernel(const dd_quality_record* __restrict__ partials, int tiles,
                                                                           dd_quality_record* __restrict__ records) {
-  __shared__ double sd[5][QTHREADS];
-  __shared__ unsigned long long su[3][QTHREADS];
-  __shared__ float sf[QTHREADS];
-  const int tid = threadIdx.x;
-  const dd_quality_record* __restrict__ p = partials + (long)blockIdx.x * tiles;
-  double d[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
-  unsigned long long u[3] = {0ull, 0ull, 0ull};
-  float mx = 0.f;
-  for (int b = tid; b < tiles; b += QTHREADS) {
-    const dd_quality_record r = p[b];
-    u[0] += r.pixels_valid; u[1] += r.windows_valid; u[2] += r.ldr_sq_err;
-    d[0] += r.se; d[1] += r.ae; d[2] += r.rse; d[3] += r.smape; d[4] += r.ssim_sum;
-    mx = fmaxf(mx, r.max_abs);
-  }
-#pragma unroll
-  for (int m = 0; m < 5; ++m) sd[m][tid] = d[m];
-#pragma unroll
-  for (int m = 0; m < 3; ++m) su[m][tid] = u[m];
-  sf[tid] = mx;
-  __syncthreads();
-  for (int half = QTHREADS / 2; half > 0; half >>= 1) {
-    if (tid < half) {
-#pragma unroll
-      for (int m = 0; m < 5; ++m) sd[m][tid] += sd[m][tid + half];
-#pragma unroll
-      for (int m = 0; m < 3; ++m) su[m][tid] += su[m][tid + half];
-      sf[tid] = fmaxf(sf[tid], sf[tid + half]);
-    }
-    __syncthreads();
-  }
-  if (tid == 0) {
-    dd_quality_record r;
-    r.pixels_valid = su[0][0]; r.windows_valid = su[1][0]; r.ldr_sq_err = su[2][0];
-    r.se = sd[0][0]; r.ae = sd[1][0]; r.rse = sd[2][0]; r.smape = sd[3][0]; r.ssim_sum = sd[4][0];
-    r.max_abs = sf[0];
-    r.reserved = 0.f;
-    records[blockIdx.x] = r;
-  }
+  frame_finalize<dd_quality_record, QU, QD, true>(partials, tiles, records);
 }
-
-inline long tiles_of(int n) { return ((long)n + QT - 1) / QT; }
 
 }  // namespace
 
 extern "C" long dd_frame_quality_scratch_bytes(int n_pairs, int H, int W) {
-  if (n_pairs < 1 || n_pairs > DD_QUALITY_MAX_PAIRS || H < 1 || W < 1) {
-    dd_set_error("dd_frame_quality_scratch_bytes: n_pairs = %d (1 .. %d), H = %d, W = %d", n_pairs, DD_QUALITY_MAX_PAIRS, H, W);
-    return DD_ERR_INVALID;
-  }
-  return (long)n_pairs * tiles_of(H) * tiles_of(W) * (long)sizeof(dd_quality_record);
+  return frame_scratch_bytes<QT, dd_quality_record>("dd_frame_quality_scratch_bytes", "n_pairs", n_pairs, DD_QUALITY_MAX_PAIRS, H, W);
 }
 
 extern "C" int dd_frame_quality(const dd_quality_pair* pairs, int n_pairs, int H, int W, const float* thresholds, float exposure, float epsilon,
@@ -335,11 +268,10 @@ extern "C" int dd_frame_quality(const dd_quality_pair* pairs, int n_pairs, int H
   DD_REQUIRE(pairs, "dd_frame_quality: null pair table");
   DD_REQUIRE(n_pairs >= 1 && n_pairs <= DD_QUALITY_MAX_PAIRS, "dd_frame_quality: n_pairs = %d (1 .. %d)", n_pairs, DD_QUALITY_MAX_PAIRS);
   DD_REQUIRE(H >= 1 && W >= 1, "dd_frame_quality: bad shape %d x %d", H, W);
-  DD_REQUIRE(tiles_of(H) <= 65535 && tiles_of(W) <= 0x7fffffffl, "dd_frame_quality: %d x %d does not fit a grid", H, W);
+  DD_REQUIRE(frame_tiles_of<QT>(H) <= 65535 && frame_tiles_of<QT>(W) <= 0x7fffffffl, "dd_frame_quality: %d x %d does not fit a grid", H, W);
   DD_REQUIRE(thresholds, "dd_frame_quality: no threshold table (thresholds is null)");
   DD_REQUIRE(((uintptr_t)thresholds & 3) == 0, "dd_frame_quality: thresholds must be 4-byte aligned");
-  DD_REQUIRE(records && ((uintptr_t)records & 7) == 0, "dd_frame_quality: records is null or not 8-byte aligned");
-  DD_REQUIRE(scratch && ((uintptr_t)scratch & 7) == 0, "dd_frame_quality: scratch is null or not 8-byte aligned");
+  if (int rc = frame_check_buffers("dd_frame_quality", records, scratch)) return rc;
   DD_REQUIRE(epsilon > 0.f, "dd_frame_quality: epsilon must be positive");
   QualityArgs a;
   for (int i = 0; i < DD_QUALITY_MAX_PAIRS; ++i) {
@@ -361,7 +293,7 @@ extern "C" int dd_frame_quality(const dd_quality_pair* pairs, int n_pairs, int H
   double e[11], sum = 0.0;
   for (int i = 0; i < 11; ++i) { e[i] = exp(-(double)((i - 5) * (i - 5)) / (2.0 * 1.5 * 1.5)); sum += e[i]; }
   for (int i = 0; i < 11; ++i) a.gauss[i] = e[i] / sum;
-  const int tx = (int)tiles_of(W), ty = (int)tiles_of(H);
+  const int tx = (int)frame_tiles_of<QT>(W), ty = (int)frame_tiles_of<QT>(H);
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   hipLaunchKernelGGL(frame_quality_kernel, dim3((unsigned)tx, (unsigned)ty, (unsigned)n_pairs), dim3(QTHREADS), 0, s, a, H, W, thresholds, exposure, epsilon,
                      reinterpret_cast<dd_quality_record*>(scratch));

@@ -4,8 +4,8 @@
 //
 //   sequence_quality_kernel          : a workgroup of 256 threads owns ST x ST pixels, one per thread (a wave's lanes are four rows of 16
 //                                      neighbours).  ONCE per pixel: the previous position from the motion pass, the offscreen test, the tap
-//                                      index and the weights (csrc/dd_motion.h): four registers for the whole launch.  Then the loop over the
-//                                      pairs, per pair:
+//                                      index and the weights (csrc/dd_frame_common.h: dd_motion_previous, the function the stabiliser
+//                                      compiles too): four registers for the whole launch.  Then the loop over the pairs, per pair:
 //                                      fetch     the pixel of `pred` and `target` and the four taps of both previous frames straight from
 //                                                global memory, all ten issued before the first is used (12-byte loads where ld == nch == 3;
 //                                                neighbouring lanes share lines)
@@ -22,19 +22,19 @@
 //   sequence_quality_finalize_kernel : one workgroup per pair adds its partial records in a fixed order (integers exactly, the rest in double).
 // No atomics at all: two runs give the same bits; a pair's record does not depend on its index or on its neighbours in the call.  Nothing but
 // the partial records and the records is written.
-#include <limits.h>
-#include <math.h>
-
-#include "dd_motion.h"
+#include "dd_frame_common.h"
 
 namespace {
 
 constexpr int ST = DD_SEQQ_TILE;               // pixels per workgroup side
-constexpr int STHREADS = 256;
-constexpr int SWAVES = STHREADS / 64;
+constexpr int STHREADS = FRAME_THREADS;
+constexpr int SWAVES = FRAME_WAVES;
+constexpr int SU = 3, SD = 6;                  // counts and sums of a dd_seqq_record
 constexpr int STABLE = DD_PREVIEW_THRESHOLDS;
 static_assert(ST * ST == STHREADS && (ST & (ST - 1)) == 0 && SWAVES == 4, "a thread owns the pixel (tid / ST, tid % ST) of the tile");
 static_assert(STABLE == 255, "the binary search takes steps of 128 .. 1 over 255 entries");
+static_assert(frame_record_is<dd_seqq_record, SU, SD, false>(offsetof(dd_seqq_record, pixels_offscreen), offsetof(dd_seqq_record, change_prediction),
+                                                             sizeof(dd_seqq_record)), "dd_seqq_record: three uint64 counts, six double sums");
 constexpr int SLEVELS = 6;                     // the levels of the search that read LDS: steps 32 .. 1
 constexpr int SNODES = 4 * ((1 << SLEVELS) - 1);      // 4 + 8 + .. + 128 entries; level l (step 32 >> l) starts at 4 * (2^l - 1)
 
@@ -48,29 +48,12 @@ struct SequenceArgs {
   float sx, sy, exposure;
 };
 
-struct __attribute__((packed, aligned(4))) Float3 { float x, y, z; };
-
-__device__ __forceinline__ bool nonfinite(float v) { return (__float_as_uint(v) & 0x7f800000u) == 0x7f800000u; }
-
-template <int NCH>
-__device__ __forceinline__ void load_pixel(const float* __restrict__ base, long q, int ld, float (&v)[NCH]) {
-  if constexpr (NCH == 3) {
-    if (ld == 3) {
-      const Float3 w = *reinterpret_cast<const Float3*>(base + 3 * q);
-      v[0] = w.x; v[1] = w.y; v[2] = w.z;
-      return;
-    }
-  }
-  const float* __restrict__ s = base + q * ld;
-#pragma unroll
-  for (int c = 0; c < NCH; ++c) v[c] = s[c];
-}
-
 // the upper two levels of the search: entries 63, 127 and 191 of the table
 struct Pivots { float t63, t127, t191; };
 
-// number of table entries <= v, as a float: the comparisons of csrc/dd_quality.hip's quantise (entry lo + step - 1 with lo a multiple of
-// 2 * step), the entry read as node j = lo / (2 * step) of its level; j doubles and takes the comparison's bit, and ends as the count
+// number of table entries <= v, as a float.  The definition it must equal is dd_png_quantise (csrc/dd_png_core.h), which the other launches
+// call: the same eight comparisons (entry lo + step - 1 with lo a multiple of 2 * step), the entry read as node j = lo / (2 * step) of its
+// level; j doubles and takes the comparison's bit, and ends as the count.  Kept apart for its data layout (the level-ordered table in LDS).
 __device__ __forceinline__ float quantise(const float* nodes, const Pivots& k, float v) {
   unsigned j = k.t127 <= v ? 1u : 0u;
   j = 2u * j + ((j ? k.t191 : k.t63) <= v ? 1u : 0u);
@@ -82,15 +65,6 @@ __device__ __forceinline__ float quantise(const float* nodes, const Pivots& k, f
 __device__ __forceinline__ float bilinear(float a00, float a01, float a10, float a11, float fx, float gx, float fy, float gy) {
 #pragma clang fp contract(off)
   return (a00 * gx + a01 * fx) * gy + (a10 * gx + a11 * fx) * fy;
-}
-
-__device__ __forceinline__ double wave_sum(double v) {
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-  return v;
-}
-__device__ __forceinline__ unsigned wave_sum(unsigned v) {
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-  return v;
 }
 
 // One pair of the tile.  q: the thread's pixel index; wave_d / wave_u: this pair's buffers of the per-wave sums.
@@ -167,7 +141,7 @@ __device__ __forceinline__ void score_pair(const dd_seqq_pair& P, const dd_motio
 
 __global__ __launch_bounds__(STHREADS) void sequence_quality_kernel(const SequenceArgs a, int H, int W, dd_seqq_record* __restrict__ partials) {
   __shared__ float thr[SNODES];                  // the table's entries 2 s j + s - 1 in the order (s = 32, 16, .. 1; j): quantise
-  __shared__ double wave_d[2][6][SWAVES];        // [pair parity][sum]
+  __shared__ double wave_d[2][SD][SWAVES];       // [pair parity][sum]
   __shared__ unsigned wave_u[2][2][SWAVES];      // [pair parity][nonfinite | valid]
   __shared__ unsigned wave_c[SWAVES];            // offscreen: the same for every pair
 
@@ -192,17 +166,9 @@ __global__ __launch_bounds__(STHREADS) void sequence_quality_kernel(const Sequen
   const long block = (long)blockIdx.y * gridDim.x + blockIdx.x, blocks = (long)gridDim.x * gridDim.y;
   auto write_partial = [&](int p) {      // thread 0, behind a barrier that follows pair p's sums
     const int b = p & 1;
-    dd_seqq_record r;
-    r.pixels_offscreen = wave_c[0] + wave_c[1] + wave_c[2] + wave_c[3];
-    r.pixels_nonfinite = wave_u[b][0][0] + wave_u[b][0][1] + wave_u[b][0][2] + wave_u[b][0][3];
-    r.pixels_valid = wave_u[b][1][0] + wave_u[b][1][1] + wave_u[b][1][2] + wave_u[b][1][3];
-    r.change_prediction = ((wave_d[b][0][0] + wave_d[b][0][1]) + wave_d[b][0][2]) + wave_d[b][0][3];
-    r.change_target = ((wave_d[b][1][0] + wave_d[b][1][1]) + wave_d[b][1][2]) + wave_d[b][1][3];
-    r.temporal_error = ((wave_d[b][2][0] + wave_d[b][2][1]) + wave_d[b][2][2]) + wave_d[b][2][3];
-    r.ldr_change_prediction = ((wave_d[b][3][0] + wave_d[b][3][1]) + wave_d[b][3][2]) + wave_d[b][3][3];
-    r.ldr_change_target = ((wave_d[b][4][0] + wave_d[b][4][1]) + wave_d[b][4][2]) + wave_d[b][4][3];
-    r.ldr_temporal_error = ((wave_d[b][5][0] + wave_d[b][5][1]) + wave_d[b][5][2]) + wave_d[b][5][3];
-    partials[(long)p * blocks + block] = r;
+    FrameSums<SU, SD, false> r;
+    frame_wave_partial<SU, SD>(r.u, r.d, {wave_c, wave_u[b][0], wave_u[b][1]}, wave_d[b]);
+    reinterpret_cast<FrameSums<SU, SD, false>*>(partials)[(long)p * blocks + block] = r;
   };
   for (int p = 0; p < a.n_pairs; ++p) {
     __syncthreads();      // the table is staged; the pair before has left its sums (two buffers: pair p + 1 fills the other one)
@@ -217,54 +183,16 @@ __global__ __launch_bounds__(STHREADS) void sequence_quality_kernel(const Sequen
   if (tid == 0) write_partial(a.n_pairs - 1);
 }
 
-// records[pair] = the sum of the pair's `tiles` partial records: thread t adds records t, t + 256, ... in order, then a fixed tree over the threads
+// records[pair] = the sum of the pair's `tiles` partial records (csrc/dd_frame_common.h: frame_finalize)
 __global__ __launch_bounds__(STHREADS) void sequence_quality_finalize_kernel(const dd_seqq_record* __restrict__ partials, int tiles,
                                                                              dd_seqq_record* __restrict__ records) {
-  __shared__ double sd[6][STHREADS];
-  __shared__ unsigned long long su[3][STHREADS];
-  const int tid = threadIdx.x;
-  const dd_seqq_record* __restrict__ p = partials + (long)blockIdx.x * tiles;
-  double d[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
-  unsigned long long u[3] = {0ull, 0ull, 0ull};
-  for (int b = tid; b < tiles; b += STHREADS) {
-    const dd_seqq_record r = p[b];
-    u[0] += r.pixels_offscreen; u[1] += r.pixels_nonfinite; u[2] += r.pixels_valid;
-    d[0] += r.change_prediction; d[1] += r.change_target; d[2] += r.temporal_error;
-    d[3] += r.ldr_change_prediction; d[4] += r.ldr_change_target; d[5] += r.ldr_temporal_error;
-  }
-#pragma unroll
-  for (int m = 0; m < 6; ++m) sd[m][tid] = d[m];
-#pragma unroll
-  for (int m = 0; m < 3; ++m) su[m][tid] = u[m];
-  __syncthreads();
-  for (int half = STHREADS / 2; half > 0; half >>= 1) {
-    if (tid < half) {
-#pragma unroll
-      for (int m = 0; m < 6; ++m) sd[m][tid] += sd[m][tid + half];
-#pragma unroll
-      for (int m = 0; m < 3; ++m) su[m][tid] += su[m][tid + half];
-    }
-    __syncthreads();
-  }
-  if (tid == 0) {
-    dd_seqq_record r;
-    r.pixels_offscreen = su[0][0]; r.pixels_nonfinite = su[1][0]; r.pixels_valid = su[2][0];
-    r.change_prediction = sd[0][0]; r.change_target = sd[1][0]; r.temporal_error = sd[2][0];
-    r.ldr_change_prediction = sd[3][0]; r.ldr_change_target = sd[4][0]; r.ldr_temporal_error = sd[5][0];
-    records[blockIdx.x] = r;
-  }
+  frame_finalize<dd_seqq_record, SU, SD, false>(partials, tiles, records);
 }
-
-inline long tiles_of(int n) { return ((long)n + ST - 1) / ST; }
 
 }  // namespace
 
 extern "C" long dd_sequence_quality_scratch_bytes(int n_pairs, int H, int W) {
-  if (n_pairs < 1 || n_pairs > DD_SEQQ_MAX_PAIRS || H < 1 || W < 1) {
-    dd_set_error("dd_sequence_quality_scratch_bytes: n_pairs = %d (1 .. %d), H = %d, W = %d", n_pairs, DD_SEQQ_MAX_PAIRS, H, W);
-    return DD_ERR_INVALID;
-  }
-  return (long)n_pairs * tiles_of(H) * tiles_of(W) * (long)sizeof(dd_seqq_record);
+  return frame_scratch_bytes<ST, dd_seqq_record>("dd_sequence_quality_scratch_bytes", "n_pairs", n_pairs, DD_SEQQ_MAX_PAIRS, H, W);
 }
 
 extern "C" int dd_sequence_quality(const dd_seqq_pair* pairs, int n_pairs, int H, int W, const float* motion, int motion_ld, float sx, float sy,
@@ -273,16 +201,10 @@ extern "C" int dd_sequence_quality(const dd_seqq_pair* pairs, int n_pairs, int H
   static_assert(sizeof(dd_seqq_pair) == 56, "include/dd_hip.h, _lib.SequenceQualityPair");
   DD_REQUIRE(pairs, "dd_sequence_quality: null pair table");
   DD_REQUIRE(n_pairs >= 1 && n_pairs <= DD_SEQQ_MAX_PAIRS, "dd_sequence_quality: n_pairs = %d (1 .. %d)", n_pairs, DD_SEQQ_MAX_PAIRS);
-  DD_REQUIRE(H >= 1 && W >= 1, "dd_sequence_quality: bad shape %d x %d", H, W);
-  DD_REQUIRE((long)H * W <= INT_MAX && H <= (1 << 24) && W <= (1 << 24) && tiles_of(H) <= 65535,
-             "dd_sequence_quality: %d x %d does not fit a grid or a 32-bit pixel index", H, W);
-  DD_REQUIRE(motion && ((uintptr_t)motion & 3) == 0, "dd_sequence_quality: motion is null or not 4-byte aligned");
-  DD_REQUIRE(motion_ld >= 2, "dd_sequence_quality: motion_ld = %d (the pass has two used channels)", motion_ld);
-  DD_REQUIRE(isfinite(sx) && isfinite(sy), "dd_sequence_quality: the motion scale is not finite");
+  if (int rc = frame_check_motion<ST>("dd_sequence_quality", H, W, motion, motion_ld, sx, sy)) return rc;
   DD_REQUIRE(thresholds && ((uintptr_t)thresholds & 3) == 0, "dd_sequence_quality: thresholds is null or not 4-byte aligned");
   DD_REQUIRE(isfinite(exposure), "dd_sequence_quality: the exposure is not finite");
-  DD_REQUIRE(records && ((uintptr_t)records & 7) == 0, "dd_sequence_quality: records is null or not 8-byte aligned");
-  DD_REQUIRE(scratch && ((uintptr_t)scratch & 7) == 0, "dd_sequence_quality: scratch is null or not 8-byte aligned");
+  if (int rc = frame_check_buffers("dd_sequence_quality", records, scratch)) return rc;
   SequenceArgs a;
   memset(&a, 0, sizeof(a));
   for (int i = 0; i < n_pairs; ++i) {
@@ -297,7 +219,7 @@ extern "C" int dd_sequence_quality(const dd_seqq_pair* pairs, int n_pairs, int H
   }
   a.motion = motion; a.thresholds = thresholds; a.motion_ld = motion_ld; a.n_pairs = n_pairs;
   a.sx = sx; a.sy = sy; a.exposure = exposure;
-  const int tx = (int)tiles_of(W), ty = (int)tiles_of(H);
+  const int tx = (int)frame_tiles_of<ST>(W), ty = (int)frame_tiles_of<ST>(H);
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   hipLaunchKernelGGL(sequence_quality_kernel, dim3((unsigned)tx, (unsigned)ty), dim3(STHREADS), 0, s, a, H, W, reinterpret_cast<dd_seqq_record*>(scratch));
   DD_LAUNCH_CHECK();

@@ -82,6 +82,17 @@ def parser():
     return p
 
 
+def short_name(key):
+    """'prediction/<Pass>' -> '<Pass>': the name of a pass in the printed tables and in the files next to the inputs."""
+    return key.split("/", 1)[1] if key.startswith("prediction/") else key
+
+
+def run_parameters(args):
+    """The options that decide what was scored, as quality.json and sequence_quality.json record them."""
+    return {"tile_size": int(args.tile_size), "tile_overlap_size": int(args.tile_overlap_size), "dtype": args.dtype, "nonfinite": args.nonfinite,
+            "tile_blend": args.tile_blend, "exposure": float(args.exposure)}
+
+
 def report_quality(args, arch, out, directory=None, targets=None, json_path=None, scorer=None):
     """--target: the predictions `out` (still on the device) against the target frame: one dd_frame_quality call, one copy of the records.
     directory: where the pictures and quality.json go (default: --input); targets: the loaded target frame (default: --target's); json_path: of the
@@ -95,19 +106,16 @@ def report_quality(args, arch, out, directory=None, targets=None, json_path=None
     maps = {}
     if args.ssim_png:
         result, maps = result
-    short = {(k.split("/", 1)[1] if k.startswith("prediction/") else k): v for k, v in result.items()}
-    for line in quality.table_lines(short):
+    for line in quality.table_lines({short_name(k): v for k, v in result.items()}):
         print(line)
     for key, ssim_map in maps.items():
-        path = os.path.join(directory, (key.split("/", 1)[1] if key.startswith("prediction/") else key) + "_ssim.png")
+        path = os.path.join(directory, short_name(key) + "_ssim.png")
         with open(path, "wb") as f:
             f.write(encode_png(quality.ssim_picture(ssim_map)))
         print(path)
     path = json_path or args.quality_json or os.path.join(directory, "quality.json")
-    document = {"tile_size": int(args.tile_size), "tile_overlap_size": int(args.tile_overlap_size), "dtype": args.dtype, "nonfinite": args.nonfinite,
-                "tile_blend": args.tile_blend, "exposure": float(args.exposure), "quality": result}
     with open(path, "w") as f:
-        json.dump(document, f, indent=1)
+        json.dump(dict(run_parameters(args), quality=result), f, indent=1)
     print(path)
     return result
 
@@ -210,7 +218,7 @@ class SequenceScore:
         from . import quality, sequence_quality
         self.parent = args.target_sequence
         self.frame_quality = quality.FrameQuality(device, exposure=args.exposure)
-        self.sequence_quality = sequence_quality.SequenceQuality(device, exposure=args.exposure, motion_scale=args.motion_scale or (-1.0, 1.0))
+        self.sequence_quality = sequence_quality.SequenceQuality(device, exposure=args.exposure, motion_scale=args.motion_scale)
         self.frames = []
 
     @staticmethod
@@ -240,8 +248,8 @@ class SequenceScore:
                 values = [f["quality"][name][key] for f in self.frames if f["quality"].get(name, {}).get(key) is not None]
                 means[key] = sum(values) / len(values) if values else None
             summary[name] = {"temporal_quality": measured.get(name), "quality": means}
-        return {"exposure": float(args.exposure), "motion_scale": list(self.sequence_quality.motion_scale), "tile_size": int(args.tile_size),
-                "tile_overlap_size": int(args.tile_overlap_size), "dtype": args.dtype, "nonfinite": args.nonfinite, "tile_blend": args.tile_blend,
+        parameters = run_parameters(args)      # (this document begins with the exposure and the motion scale)
+        return {"exposure": parameters.pop("exposure"), "motion_scale": list(self.sequence_quality.motion_scale), **parameters,
                 "temporal": stabilizer.parameters() if stabilizer is not None else None, "frames": self.frames, "summary": summary}
 
 
@@ -323,7 +331,7 @@ def main(args):
             guides = [temporal.parse_guide(g) for g in (args.temporal_guide or [])]
             stabilizer = temporal.TemporalStabilizer("cuda", alpha=0.8 if args.temporal_alpha is None else args.temporal_alpha,
                                                      gamma=1.0 if args.temporal_gamma is None else args.temporal_gamma,
-                                                     motion_scale=args.motion_scale or (-1.0, 1.0), guides=guides)
+                                                     motion_scale=args.motion_scale, guides=guides)
         except ValueError as e:
             raise SystemExit("--temporal: %s" % e)
     run = Run(args)
@@ -338,8 +346,7 @@ def main(args):
         print(path)
     if score is not None:
         document = score.document(args, stabilizer)
-        measured = {(k.split("/", 1)[1] if k.startswith("prediction/") else k): v["temporal_quality"] for k, v in document["summary"].items()
-                    if v["temporal_quality"] is not None}
+        measured = {short_name(k): v["temporal_quality"] for k, v in document["summary"].items() if v["temporal_quality"] is not None}
         for line in table_lines(measured):
             print(line)
         path = args.sequence_quality_json or os.path.join(args.input_sequence, "sequence_quality.json")

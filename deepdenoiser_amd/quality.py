@@ -16,6 +16,7 @@ import numpy as np
 import torch
 
 from . import _lib as L
+from . import frame_launch
 from . import metrics as M
 from . import openexr
 from .naming import Naming
@@ -36,11 +37,7 @@ class FrameQuality:
     def _buffers_of(self, n, H, W):
         key = (n, H, W)
         if key not in self._buffers:
-            nbytes = self.lib.dd_frame_quality_scratch_bytes(n, H, W)
-            if nbytes < 0:
-                L.check(int(nbytes))
-            self._buffers[key] = (torch.zeros((n * C.sizeof(L.QualityRecord),), dtype=torch.uint8, device=self.device),
-                                  torch.empty(((nbytes + 7) // 8,), dtype=torch.int64, device=self.device))
+            self._buffers[key] = frame_launch.record_buffers(self.lib.dd_frame_quality_scratch_bytes, L.QualityRecord, n, H, W, self.device)
         return self._buffers[key]
 
     def launch(self, pairs, ssim_maps=False):
@@ -53,11 +50,7 @@ class FrameQuality:
         table = (L.QualityPair * len(pairs))()
         for i, (p, t) in enumerate(pairs):
             for what, v in (("prediction", p), ("target", t)):
-                if v.dim() != 3 or tuple(v.shape[:2]) != (H, W) or v.dtype != torch.float32 or v.device != self.device:
-                    raise ValueError("pair %d: the %s must be a float32 [%d,%d,C] tensor on %s, not %s %s on %s"
-                                     % (i, what, H, W, self.device, v.dtype, tuple(v.shape), v.device))
-                if v.stride(2) != 1 or v.stride(1) < v.shape[2] or v.stride(0) != W * v.stride(1):
-                    raise ValueError("pair %d: the %s must be a dense [H,W,ld] frame or a [..., :C] view of one" % (i, what))
+                frame_launch.check_frame("pair %d: the %s" % (i, what), v, H, W, self.device, least=0)      # (the channels: below, on both sides)
             if p.shape[2] != t.shape[2] or p.shape[2] not in (1, 3):
                 raise ValueError("pair %d: 1 or 3 channels on both sides are expected, not %d and %d" % (i, p.shape[2], t.shape[2]))
             table[i] = L.QualityPair(p.data_ptr(), t.data_ptr(), p.stride(1), t.stride(1), p.shape[2])
@@ -80,8 +73,7 @@ class FrameQuality:
             raise ValueError("no target for %s" % ", ".join(missing))
         pairs = [(self._resident(predictions[n]), self._resident(targets[n])) for n in names]
         records, maps = self.launch(pairs, ssim_maps)
-        host = records.cpu().numpy().tobytes()
-        recs = (L.QualityRecord * len(names)).from_buffer_copy(host)
+        recs = frame_launch.read_records(records, L.QualityRecord, len(names))
         out = {n: figures(recs[i], *pairs[i][0].shape) for i, n in enumerate(names)}
         if ssim_maps:
             return out, ({} if maps is None else dict(zip(names, maps)))

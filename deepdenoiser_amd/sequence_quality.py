@@ -13,13 +13,13 @@ prediction follows the target's own change (change_target) less well.  change_pr
 and |T_t - warp(T_t-1)|; with the wrong motion convention change_target explodes.  The ldr_ figures are the same on the 8-bit sRGB bytes of
 `exposure * value` (metrics.preview_thresholds), divided by 255.  A pixel whose previous position lies outside the frame (offscreen) or that
 reads a NaN / Inf in one of the four images (nonfinite) adds to nothing."""
-import ctypes as C
 import math
 
 import numpy as np
 import torch
 
 from . import _lib as L
+from . import frame_launch
 from . import metrics as M
 
 COUNTS = ("pixels_offscreen", "pixels_nonfinite", "pixels_valid")
@@ -28,16 +28,14 @@ LDR_SUMS = ("ldr_change_prediction", "ldr_change_target", "ldr_temporal_error")
 
 
 class SequenceQuality:
-    def __init__(self, device, exposure=1.0, motion_scale=(-1.0, 1.0)):
+    def __init__(self, device, exposure=1.0, motion_scale=None):
         """exposure: the factor in front of the 8-bit quantisation of the ldr_ figures.  motion_scale (sx, sy): previous position = (x + sx *
-        motion channel 0, y + sy * motion channel 1); the default is the stabiliser's (temporal.py: an unverified reading of Cycles' Vector
+        motion channel 0, y + sy * motion channel 1); the default is the stabiliser's (frame_launch.MOTION_SCALE, temporal.py: an unverified reading of Cycles' Vector
         pass)."""
         self.exposure = float(exposure)
         if not math.isfinite(self.exposure):
             raise ValueError("exposure must be finite, not %r" % (exposure,))
-        self.motion_scale = tuple(float(v) for v in motion_scale)
-        if len(self.motion_scale) != 2 or not all(math.isfinite(v) for v in self.motion_scale):
-            raise ValueError("motion_scale must be two finite numbers, not %r" % (motion_scale,))
+        self.motion_scale = frame_launch.motion_scale(motion_scale)
         self.lib = L.load()
         self._thresholds = torch.from_numpy(M.preview_thresholds()).to(torch.device(device))
         self.device = self._thresholds.device      # (with its index: what the tensors of a frame are compared with)
@@ -48,17 +46,6 @@ class SequenceQuality:
     def reset(self):
         """Forget the history: the next frame is not measured and becomes the history.  summary() keeps what was measured."""
         self._signature, self._previous, self._records, self._scratch = None, None, None, None
-
-    def _check(self, what, v, H, W, channels=None, least=1):
-        if not torch.is_tensor(v) or v.dim() != 3 or tuple(v.shape[:2]) != (H, W) or v.dtype != torch.float32 or v.device != self.device:
-            raise ValueError("%s must be a float32 [%d,%d,C] tensor on %s, not %s" % (what, H, W, self.device, (
-                "%s %s on %s" % (v.dtype, tuple(v.shape), v.device)) if torch.is_tensor(v) else type(v).__name__))
-        if v.stride(2) != 1 or v.stride(1) < v.shape[2] or v.stride(0) != W * v.stride(1):
-            raise ValueError("%s must be a dense [H,W,ld] frame or a [..., :C] view of one" % what)
-        if channels is not None and v.shape[2] not in channels:
-            raise ValueError("%s: 1 or 3 channels are expected, not %d" % (what, v.shape[2]))
-        if v.shape[2] < least:
-            raise ValueError("%s: at least %d channels are expected, not %d" % (what, least, v.shape[2]))
 
     def measure(self, predictions, targets, motion):
         """predictions, targets: {name: float32 [H,W,C] device tensor, C 1 or 3}; every prediction is scored against the target of its name (a
@@ -77,11 +64,11 @@ class SequenceQuality:
             raise ValueError("%s must be a float32 [H,W,C] tensor" % names[0])
         H, W = int(first.shape[0]), int(first.shape[1])
         for n in names:
-            self._check(n, predictions[n], H, W, channels=(1, 3))
-            self._check("the target of %s" % n, targets[n], H, W, channels=(1, 3))
+            frame_launch.check_frame(n, predictions[n], H, W, self.device, channels=(1, 3))
+            frame_launch.check_frame("the target of %s" % n, targets[n], H, W, self.device, channels=(1, 3))
             if targets[n].shape[2] != predictions[n].shape[2]:
                 raise ValueError("%s has %d channels, its target %d" % (n, predictions[n].shape[2], targets[n].shape[2]))
-        self._check("motion", motion, H, W, least=2)
+        frame_launch.check_frame("motion", motion, H, W, self.device, least=2)
         signature = (H, W, tuple((n, int(predictions[n].shape[2])) for n in names))
         if signature != self._signature:
             self._start(signature, names, predictions, targets)
@@ -90,8 +77,7 @@ class SequenceQuality:
         for n in names:                               # (behind the launch on the same stream: it has read the previous frame)
             self._previous[n][0].copy_(predictions[n])
             self._previous[n][1].copy_(targets[n])
-        host = self._records.cpu().numpy().tobytes()
-        recs = (L.SequenceQualityRecord * len(names)).from_buffer_copy(host)
+        recs = frame_launch.read_records(self._records, L.SequenceQualityRecord, len(names))
         out = {}
         for i, (n, channels) in enumerate(signature[2]):
             total = self._totals.setdefault(n, [channels, 0, {k: 0 for k in COUNTS + SUMS + LDR_SUMS}])
@@ -126,11 +112,8 @@ class SequenceQuality:
         self._signature = signature
         self._previous = {n: (predictions[n].clone(memory_format=torch.contiguous_format), targets[n].clone(memory_format=torch.contiguous_format))
                           for n in names}
-        nbytes = self.lib.dd_sequence_quality_scratch_bytes(len(names), H, W)
-        if nbytes < 0:
-            L.check(int(nbytes))
-        self._records = torch.zeros((len(names) * C.sizeof(L.SequenceQualityRecord),), dtype=torch.uint8, device=self.device)
-        self._scratch = torch.empty(((nbytes + 7) // 8,), dtype=torch.int64, device=self.device)
+        self._records, self._scratch = frame_launch.record_buffers(self.lib.dd_sequence_quality_scratch_bytes, L.SequenceQualityRecord, len(names), H, W,
+                                                                   self.device)
 
     def summary(self):
         """-> {name: the figures of measure() from the raw records of all measured frames added in float64 (frames weigh by their valid values),

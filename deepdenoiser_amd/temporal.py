@@ -15,7 +15,6 @@ keep the current value bit for bit.  One launch for all passes of a frame and no
 alpha = 0.8 and gamma = 1.0 are choices, not measured optima.  The default motion_scale (-1, +1) encodes this reading of Cycles' Vector
 pass: X, Y = current raster position minus previous raster position, in pixels, and raster y points up while rows count down.  It has not
 been checked against a render (there is no Blender on the build machine); that is why it is an option."""
-import ctypes as C
 import math
 import os
 import re
@@ -23,6 +22,7 @@ import re
 import torch
 
 from . import _lib as L
+from . import frame_launch
 
 COUNTS = ("pixels_offscreen", "pixels_guide", "pixels_nonfinite", "pixels_blended", "values_clamped")
 SUMS = ("change", "flicker_before", "flicker_after")
@@ -52,10 +52,10 @@ def frame_directories(parent):
 
 
 class TemporalStabilizer:
-    def __init__(self, device, alpha=0.8, gamma=1.0, motion_scale=(-1.0, 1.0), guides=()):
+    def __init__(self, device, alpha=0.8, gamma=1.0, motion_scale=None, guides=()):
         """alpha: the weight of the (clamped) history in a blended pixel, 0 .. 1.  gamma >= 0: the clamp's half width in standard deviations of
         the 3 x 3 neighbourhood.  Both defaults are choices, not measured optima.  motion_scale (sx, sy): previous position = (x + sx * motion
-        channel 0, y + sy * motion channel 1); the default is an unverified reading of Cycles' Vector pass (the module's docstring).  guides:
+        channel 0, y + sy * motion channel 1); the default, frame_launch.MOTION_SCALE = (-1, +1), is an unverified reading of Cycles' Vector pass (the module's docstring).  guides:
         a sequence of (pass name, tolerance), at most 4: a pixel whose guide pass differs from the previous frame's at the nearest previous
         pixel by more than the tolerance in any channel is not blended."""
         self.alpha, self.gamma = float(alpha), float(gamma)
@@ -63,9 +63,7 @@ class TemporalStabilizer:
             raise ValueError("alpha must be 0 .. 1, not %r" % (alpha,))
         if not (self.gamma >= 0.0 and math.isfinite(self.gamma)):
             raise ValueError("gamma must be finite and >= 0, not %r" % (gamma,))
-        self.motion_scale = tuple(float(v) for v in motion_scale)
-        if len(self.motion_scale) != 2 or not all(math.isfinite(v) for v in self.motion_scale):
-            raise ValueError("motion_scale must be two finite numbers, not %r" % (motion_scale,))
+        self.motion_scale = frame_launch.motion_scale(motion_scale)
         self.guides = tuple((str(name), float(tolerance)) for name, tolerance in guides)
         if len(self.guides) > L.TEMPORAL_MAX_GUIDES:
             raise ValueError("at most %d guides are expected, not %d" % (L.TEMPORAL_MAX_GUIDES, len(self.guides)))
@@ -85,17 +83,6 @@ class TemporalStabilizer:
     def parameters(self):
         return {"alpha": self.alpha, "gamma": self.gamma, "motion_scale": list(self.motion_scale), "guides": [list(g) for g in self.guides]}
 
-    def _check(self, what, v, H, W, channels=None, least=1):
-        if not torch.is_tensor(v) or v.dim() != 3 or tuple(v.shape[:2]) != (H, W) or v.dtype != torch.float32 or v.device != self.device:
-            raise ValueError("%s must be a float32 [%d,%d,C] tensor on %s, not %s" % (what, H, W, self.device, (
-                "%s %s on %s" % (v.dtype, tuple(v.shape), v.device)) if torch.is_tensor(v) else type(v).__name__))
-        if v.stride(2) != 1 or v.stride(1) < v.shape[2] or v.stride(0) != W * v.stride(1):
-            raise ValueError("%s must be a dense [H,W,ld] frame or a [..., :C] view of one" % what)
-        if channels is not None and v.shape[2] not in channels:
-            raise ValueError("%s: 1 or 3 channels are expected, not %d" % (what, v.shape[2]))
-        if v.shape[2] < least:
-            raise ValueError("%s: at least %d channels are expected, not %d" % (what, least, v.shape[2]))
-
     def stabilize(self, predictions, motion, guide_frames=None):
         """predictions: {name: float32 [H,W,C] device tensor, C 1 or 3} (what Predictor.predict_frame returns, without the recombined entries);
         motion: the [H,W,>=2] tensor of the frame; guide_frames: {guide pass: [H,W,C] tensor} for every guide.  -> the same keys with the
@@ -110,13 +97,13 @@ class TemporalStabilizer:
             raise ValueError("%s must be a float32 [H,W,C] tensor" % names[0])
         H, W = int(first.shape[0]), int(first.shape[1])
         for n in names:
-            self._check(n, predictions[n], H, W, channels=(1, 3))
-        self._check("motion", motion, H, W, least=2)
+            frame_launch.check_frame(n, predictions[n], H, W, self.device, channels=(1, 3))
+        frame_launch.check_frame("motion", motion, H, W, self.device, least=2)
         guide_frames = guide_frames or {}
         for g, _ in self.guides:
             if g not in guide_frames:
                 raise ValueError("no frame for the guide pass %s" % g)
-            self._check("guide %s" % g, guide_frames[g], H, W, channels=(1, 3))
+            frame_launch.check_frame("guide %s" % g, guide_frames[g], H, W, self.device, channels=(1, 3))
         signature = (H, W, tuple((n, int(predictions[n].shape[2])) for n in names), tuple(int(guide_frames[g].shape[2]) for g, _ in self.guides))
         if signature != self._signature:
             self._start(signature, names, predictions, guide_frames)
@@ -147,19 +134,14 @@ class TemporalStabilizer:
         for n in names:
             self._sets[0][n].copy_(predictions[n])
         self._guide_previous = {g: guide_frames[g].clone(memory_format=torch.contiguous_format) for g, _ in self.guides}
-        nbytes = self.lib.dd_temporal_scratch_bytes(len(names), H, W)
-        if nbytes < 0:
-            L.check(int(nbytes))
-        self._records = torch.zeros((len(names) * C.sizeof(L.TemporalRecord),), dtype=torch.uint8, device=self.device)
-        self._scratch = torch.empty(((nbytes + 7) // 8,), dtype=torch.int64, device=self.device)
+        self._records, self._scratch = frame_launch.record_buffers(self.lib.dd_temporal_scratch_bytes, L.TemporalRecord, len(names), H, W, self.device)
 
     def report(self):
         """ONE device-to-host copy of the records of the last frame -> {name: {the five counts, "change", "flicker_before", "flicker_after"}}: the
         last three are means per blended value (pixels_blended * channels), None when nothing was blended (a frame that passed through)."""
         if self._records is None:
             raise RuntimeError("report() needs a frame: call stabilize() first")
-        host = self._records.cpu().numpy().tobytes()
-        recs = (L.TemporalRecord * len(self._names)).from_buffer_copy(host)
+        recs = frame_launch.read_records(self._records, L.TemporalRecord, len(self._names))
         return {n: figures(recs[i], channels) for i, (n, channels) in enumerate(self._signature[2])}
 
 

@@ -786,8 +786,8 @@ int dd_temporal_stabilize(const dd_temporal_pass* passes, int n_passes, const dd
  * frame and its ground truth), `pred_previous` and `target_previous` (the same of the frame before), fp32 images [H,W,ld] of which the first
  * nch (1 or 3) channels are used, every image with an ld >= nch of its own (a 1-channel pass is a [..., :1] view of a 3-wide frame: ld 3,
  * nch 1).  motion: fp32 [H,W,motion_ld] of the CURRENT frame, channels 0 and 1 used.  pairs is a HOST array (copied by value).
- * Per pixel (x = column, y = row), decided ONCE and shared by all pairs, in fp32 with one rounding per operation (csrc/dd_motion.h; the rules
- * of dd_temporal_stabilize without its guides):
+ * Per pixel (x = column, y = row), decided ONCE and shared by all pairs, in fp32 with one rounding per operation (dd_motion_previous of
+ * csrc/dd_frame_common.h, the function dd_temporal_stabilize compiles too: its rules without its guides):
  *   px = x + sx * motion[y,x,0], py = y + sy * motion[y,x,1]: where the pixel was in the previous frame
  *   offscreen    : px or py not finite or outside [0, W-1] x [0, H-1]
  *   taps         : x0 = floor(px), fx = px - x0, y0 = floor(py), fy = py - y0; (y0,x0) (y0,x0+1) (y0+1,x0) (y0+1,x0+1), indices clamped

@@ -149,6 +149,7 @@ SHAPES = [
     ("one_tile", TH + 10, TW + 10, [(3, 3, 3, 10)]),
     ("tile_plus_11_by_plus_9", TH + 11, TW + 9, [(3, 3, 3, 11), (1, 1, 2, 12)]),
     ("two_tiles_and_a_row", 2 * TH + 10 + 1, TW + 10 - 1, [(3, 3, 3, 13)]),
+    ("257_tiles", 11, 8193, [(3, 3, 3, 30), (1, 3, 1, 31)]),      # the second round of the finalize kernel's strided add
 ]
 
 

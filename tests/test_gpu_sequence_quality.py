@@ -103,6 +103,7 @@ CASES = [
     (40, 1, MIX, False, 1.0),
     (45, 70, MIX, True, 1.0),
     (33, 37, MIX, True, 2.0),
+    (1, 4097, MIX, False, 1.0),               # 257 tiles: the second round of the finalize kernel's strided add
 ]
 
 

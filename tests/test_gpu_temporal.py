@@ -101,6 +101,7 @@ CASES = [
     (40, 1, MIX, 0, False, 0.8, 0.5),
     (45, 70, MIX, 2, True, 0.8, 1.0),
     (33, 37, MIX, 0, True, 1.0, 0.5),
+    (1, 4097, MIX, 2, False, 0.8, 1.0),       # 257 tiles: the second round of the finalize kernel's strided add
 ]
 
 

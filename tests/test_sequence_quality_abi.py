@@ -42,12 +42,14 @@ def test_symbols_are_declared_built_and_exported(lib):
     for word in ("offscreen takes precedence", "a tap with weight 0 still counts", "they add up to H * W", "Refused with a negative status", "No host sync"):
         assert word in comment, word
     from deepdenoiser_amd import build
-    assert "dd_sequence_quality.hip" in build.SOURCES and "dd_motion.h" in build.HEADERS
+    assert "dd_sequence_quality.hip" in build.SOURCES and "dd_frame_common.h" in build.HEADERS and "dd_motion.h" not in build.HEADERS
     assert build.NO_SCRATCH["dd_sequence_quality.hip"] == ("sequence_quality_kernel", "sequence_quality_finalize_kernel")
     source = open(os.path.join(build.CSRC, "dd_sequence_quality.hip")).read()
-    assert '#include "dd_motion.h"' in source and "dd_motion_previous(" in source
+    assert '#include "dd_frame_common.h"' in source and "dd_motion_previous(" in source
     assert "asm" not in source.replace("assembly", "") and "atomic" not in source.replace("No atomics", "").replace("floating-point atomics", "")
-    assert "dd_motion" not in open(os.path.join(build.CSRC, "dd_temporal.hip")).read()      # the stabiliser's launch is as it was
+    stabiliser = open(os.path.join(build.CSRC, "dd_temporal.hip")).read()                # the stabiliser compiles the same function: one rule
+    assert '#include "dd_frame_common.h"' in stabiliser and "dd_motion_previous(" in stabiliser and "floorf(px)" not in stabiliser
+    assert not os.path.exists(os.path.join(build.CSRC, "dd_motion.h"))
     T = _lib.SEQQ_TILE
     tiles = lambda n: (n + T - 1) // T                                              # noqa: E731
     assert lib.dd_sequence_quality_scratch_bytes(15, 1080, 1920) == 15 * tiles(1080) * tiles(1920) * 72
