@@ -19,7 +19,7 @@ SOURCES = ["dd_conv_igemm.hip", "dd_conv_wgrad.hip", "dd_pointwise.hip", "dd_com
            "dd_frame_statistics.hip", "dd_frame_importance.hip", "dd_importance_update.hip", "dd_exr_decode.hip", "dd_exr_inflate.hip",
            "dd_exr_encode.hip", "dd_exr_deflate.hip", "dd_png_encode.hip", "dd_temporal.hip", "dd_sequence_quality.hip"]
 VERSION_SRC = "dd_version.hip"
-HEADERS = ["dd_common.h", "dd_compose_stream.h", "dd_loss_common.h", "dd_metrics_stage.h", "dd_inflate_core.h", "dd_deflate_core.h", "dd_png_core.h", "dd_frame_common.h", os.path.join("..", "..", "include", "dd_hip.h")]
+HEADERS = ["dd_common.h", "dd_compose_stream.h", "dd_loss_common.h", "dd_metrics_stage.h", "dd_inflate_core.h", "dd_deflate_core.h", "dd_deflate_launch.h", "dd_png_core.h", "dd_frame_common.h", os.path.join("..", "..", "include", "dd_hip.h")]
 LIB = os.path.join(HERE, "libdd_hip.so")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function"]
 # Kernels that must not use scratch memory.  (1) Kernels whose long-lived accumulators are updated by in-place inline-asm MFMAs (no hazard

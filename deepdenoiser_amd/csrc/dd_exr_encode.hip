@@ -2,7 +2,7 @@
 // launch turns the fp32 planes of a whole frame's passes into the bytes of every scan-line chunk, at the chunk's place in one staged buffer:
 // HALF or FLOAT samples, per row and per channel in name order, and for a coded chunk the even / odd byte split and the delta predictor, so
 // that dd_exr_deflate (dd_exr_deflate.hip, the next launch on the same stream) finds what zlib would be given
-// (deepdenoiser_amd/openexr.py: _interleave_and_predict, DeviceEncoder).
+// (deepdenoiser_amd/openexr/codec.py: _interleave_and_predict; openexr/encode.py: DeviceEncoder).
 //
 // Shape.  One workgroup of 256 threads per chunk (1 or 16 scan lines), all files of a batch in one grid.  A chunk holds n = rows * row_bytes
 // bytes at a 16-byte aligned offset and owns the bytes up to the next multiple of 16.  A thread builds 16 consecutive OUTPUT bytes and stores

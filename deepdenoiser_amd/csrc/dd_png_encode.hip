@@ -12,14 +12,13 @@
 // of 16 as zero.  All byte decisions are dd_png_core.h, shared with the CPU build (tests/png_core_main.cpp).
 // LDS: the table 1 KB, two row buffers of DD_PNG_MAX_ROW_BYTES, the staging buffer of DD_PNG_STAGE_BYTES: 61 KB, two workgroups per CU.
 //
-// png_deflate_kernel.  The shape of exr_deflate_kernel (dd_exr_deflate.hip): one wave per segment, all segments of all passes in one launch,
-// the coder core dd_deflate_core.h in its segment framing: a raw-deflate body that ends on a byte border with an empty stored block, or, for a
-// file's last segment, with the final block; the segment's Adler-32 goes to the host.
+// png_deflate_kernel.  The shape of exr_deflate_kernel (dd_exr_deflate.hip; what the two share is dd_deflate_launch.h): one wave per segment,
+// all segments of all passes in one launch, the coder core dd_deflate_core.h in its segment framing: a raw-deflate body that ends on a
+// byte border with an empty stored block, or, for a file's last segment, with the final block; the segment's Adler-32 goes to the host.
 //
 // Both tables of either launch live in device memory, so the kernels trust no record: one that does not fit its image or the buffers writes
 // nothing (pack) or gets DD_DEFLATE_RECORD (deflate); the tests are uniform over the workgroup.  Plain C++: no inline assembly, no scratch.
-#include "dd_common.h"
-#include "dd_deflate_core.h"
+#include "dd_deflate_launch.h"
 #include "dd_png_core.h"
 
 namespace {
@@ -28,8 +27,6 @@ namespace {
 
 constexpr int kThreads = 256;
 constexpr int kMaxPlaneChannels = 32;
-constexpr int kLanes = DD_DEFLATE_LANES;
-constexpr long kSliceBytes = (long)DD_DEFLATE_BLOCK_TOKENS * 4;
 
 // what both the host check and the kernel ask of an image record and of a segment of it -> the segment's bytes, or 0
 __host__ __device__ __forceinline__ bool image_fits(const dd_png_image& f) {
@@ -86,19 +83,6 @@ __global__ __launch_bounds__(kThreads) void png_pack_kernel(const dd_png_segment
   for (int i0 = tid * 16; i0 < n16; i0 += kThreads * 16) *reinterpret_cast<uint4*>(out + i0) = *reinterpret_cast<const uint4*>(stage + i0);
 }
 
-struct WaveOut {
-  unsigned char* at0;      // 16-byte aligned
-  __device__ __forceinline__ void word(int at, unsigned v) { *reinterpret_cast<unsigned*>(at0 + at) = v; }
-  __device__ __forceinline__ void byte(int at, unsigned v) { at0[at] = (unsigned char)v; }
-};
-
-__host__ __device__ __forceinline__ bool stream_fits(const dd_png_stream& r, long src_total, long out_bytes) {
-  const bool source_fits = r.src_bytes >= 1 && r.src_bytes <= DD_DEFLATE_MAX_BYTES && r.src_offset >= 0 && r.src_offset <= src_total - r.src_bytes;
-  const bool capacity_fits = r.dst_capacity >= 0 && r.dst_capacity <= DD_DEFLATE_MAX_BYTES;
-  return source_fits && capacity_fits && (r.last == 0 || r.last == 1) && r.dst_offset >= 0 && (r.dst_offset & 15) == 0 &&
-         r.dst_offset <= out_bytes - (((long)r.dst_capacity + 15) & ~15l);
-}
-
 __global__ __launch_bounds__(kLanes) void png_deflate_kernel(const dd_png_stream* __restrict__ streams, const unsigned char* __restrict__ src, long src_total,
                                                              unsigned char* out, long out_bytes, unsigned* workspace, int* __restrict__ status,
                                                              int* __restrict__ sizes, unsigned* __restrict__ adler) {
@@ -106,7 +90,7 @@ __global__ __launch_bounds__(kLanes) void png_deflate_kernel(const dd_png_stream
   const int lane = threadIdx.x;
   const dd_png_stream r = streams[blockIdx.x];
   // ---- the record is checked before anything is read or written through it (uniform: the wave leaves together)
-  if (!stream_fits(r, src_total, out_bytes)) {
+  if (!(deflate_record_fits(r, src_total, out_bytes) && (r.last == 0 || r.last == 1))) {
     if (lane == 0) {
       status[blockIdx.x] = DD_DEFLATE_RECORD;
       sizes[blockIdx.x] = 0;
@@ -174,35 +158,16 @@ extern "C" int dd_png_pack(const dd_png_segment* segments_host, const dd_png_seg
   return DD_OK;
 }
 
-extern "C" long dd_png_deflate_workspace(int n_streams) { return n_streams > 0 ? (long)n_streams * kSliceBytes : 0l; }
+extern "C" long dd_png_deflate_workspace(int n_streams) { return deflate_workspace_bytes(n_streams); }
 
 extern "C" int dd_png_deflate(const dd_png_stream* streams_host, const dd_png_stream* streams, int n_streams, const void* src, long src_total, void* out,
                               long out_bytes, void* workspace, long workspace_bytes, int* status, int* sizes, unsigned* adler, dd_stream stream) {
-  DD_REQUIRE(n_streams >= 0, "dd_png_deflate: n_streams=%d", n_streams);
-  if (n_streams == 0) return DD_OK;
-  DD_REQUIRE(streams_host && streams, "dd_png_deflate: null stream table");
-  DD_REQUIRE(src && out && workspace && status && sizes && adler, "dd_png_deflate: null source, output, workspace, status, size or adler array");
-  DD_REQUIRE((reinterpret_cast<unsigned long long>(out) & 15ull) == 0ull && (reinterpret_cast<unsigned long long>(workspace) & 3ull) == 0ull,
-             "dd_png_deflate: the output is not 16-byte aligned or the workspace not 4-byte aligned");
-  DD_REQUIRE(workspace_bytes >= dd_png_deflate_workspace(n_streams), "dd_png_deflate: workspace_bytes=%ld, %d streams need %ld", workspace_bytes, n_streams,
-             dd_png_deflate_workspace(n_streams));
-  {
-    const char* s0 = static_cast<const char*>(src);
-    const char* d0 = static_cast<const char*>(out);
-    DD_REQUIRE(src_total < 0 || out_bytes < 0 || s0 + src_total <= d0 || d0 + out_bytes <= s0,
-               "dd_png_deflate: the source (%ld bytes) and the output (%ld bytes) overlap", src_total, out_bytes);
-  }
-  for (int k = 0; k < n_streams; ++k) {
-    const dd_png_stream& r = streams_host[k];
-    DD_REQUIRE(r.src_bytes >= 1 && r.src_bytes <= DD_DEFLATE_MAX_BYTES, "dd_png_deflate: stream %d: src_bytes=%d (1 .. %d)", k, r.src_bytes, DD_DEFLATE_MAX_BYTES);
-    DD_REQUIRE(r.dst_capacity >= 0 && r.dst_capacity <= DD_DEFLATE_MAX_BYTES, "dd_png_deflate: stream %d: dst_capacity=%d", k, r.dst_capacity);
-    DD_REQUIRE(r.last == 0 || r.last == 1, "dd_png_deflate: stream %d: last=%d (0 or 1)", k, r.last);
-    DD_REQUIRE(r.src_offset >= 0 && r.src_offset <= src_total - r.src_bytes, "dd_png_deflate: stream %d: src_offset=%lld (%d bytes) leaves the %ld source bytes",
-               k, r.src_offset, r.src_bytes, src_total);
-    DD_REQUIRE(r.dst_offset >= 0 && (r.dst_offset & 15) == 0, "dd_png_deflate: stream %d: dst_offset=%lld is negative or not 16-byte aligned", k, r.dst_offset);
-    DD_REQUIRE(r.dst_offset <= out_bytes - (((long)r.dst_capacity + 15) & ~15l), "dd_png_deflate: stream %d: dst_offset=%lld (capacity %d) leaves the %ld output bytes",
-               k, r.dst_offset, r.dst_capacity, out_bytes);
-  }
+  const int rc = deflate_check("dd_png_deflate", streams_host, streams, n_streams, src, src_total, out, out_bytes, workspace, workspace_bytes,
+                               status && sizes && adler, "status, size or adler array", [](int k, const dd_png_stream& r) {
+                                 DD_REQUIRE(r.last == 0 || r.last == 1, "dd_png_deflate: stream %d: last=%d (0 or 1)", k, r.last);
+                                 return DD_OK;
+                               });
+  if (rc != DD_OK || n_streams == 0) return rc;
   hipLaunchKernelGGL(png_deflate_kernel, dim3(n_streams), dim3(kLanes), 0, S(stream), streams, reinterpret_cast<const unsigned char*>(src), src_total,
                      reinterpret_cast<unsigned char*>(out), out_bytes, reinterpret_cast<unsigned*>(workspace), status, sizes, adler);
   DD_LAUNCH_CHECK();

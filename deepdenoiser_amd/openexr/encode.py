@@ -7,10 +7,11 @@ import struct
 import numpy as np
 
 from .. import _lib as L
+from ..batch_encode import BatchEncoder, slot_layout
 from .codec import (_CODEC_NAMES, _LINES, _PIXEL, NO_COMPRESSION, RLE_COMPRESSION, ZIP_COMPRESSION, ZIPS_COMPRESSION, ExrError, _header,
                     _image_channels, _image_planes, write_exr)
 from .records import (CHUNK_DTYPE, DEFLATE_OK, DEFLATE_RAW, DEFLATE_STREAM_DTYPE, MAX_FILE_CHANNELS, MAX_STREAM_BYTES, SOURCE_DTYPE,
-                      _STAGE_ALIGN, _align, fill_row, timed)
+                      _align, fill_row)
 
 HALF, FLOAT = 1, 2                                              # pixel types of a written channel
 _TYPE_NAMES = {"half": HALF, "float": FLOAT, HALF: HALF, FLOAT: FLOAT}
@@ -106,13 +107,8 @@ def assemble(plan, statuses, sizes, slots):
 def _tables_layout(plans):
     """Where everything of a batch lies.  The slot bytes of the files follow one another ("bases", "total" of them), so do their chunks in
     the tables ("first_chunk"); the tables buffer holds chunks | sources | streams | the chunks of the second pack launch."""
-    bases, first_chunk, at, n_chunks = [], [], 0, 0
-    for p in plans:
-        bases.append(at)
-        first_chunk.append(n_chunks)
-        at += p.slot_bytes
-        n_chunks += len(p.chunks)
-    layout = {"bases": bases, "first_chunk": first_chunk, "total": max(at, _STAGE_ALIGN), "n_chunks": n_chunks, "n_files": len(plans)}
+    bases, first_chunk, total, n_chunks = slot_layout(plans, lambda p: len(p.chunks))
+    layout = {"bases": bases, "first_chunk": first_chunk, "total": total, "n_chunks": n_chunks, "n_files": len(plans)}
     layout["sources_at"] = _align(n_chunks * CHUNK_DTYPE.itemsize)
     layout["streams_at"] = _align(layout["sources_at"] + len(plans) * SOURCE_DTYPE.itemsize)
     layout["redo_at"] = _align(layout["streams_at"] + n_chunks * DEFLATE_STREAM_DTYPE.itemsize)
@@ -140,47 +136,23 @@ def _fill_tables(host, layout, plans, pointers, plane_channels):
     return chunk_table
 
 
-class DeviceEncoder:
-    """fp32 device planes to EXR files, all files of a call in one batch: one dd_exr_pack launch, one dd_exr_deflate launch, one
-    synchronisation to read statuses and sizes, a second dd_exr_pack launch (coded = 0) for exactly the chunks that did not shrink, written
-    straight into their slots, one download into a pinned buffer, and the files written on `threads` threads (at most 16).  The planes read
-    back bit-identical through read_image (FLOAT) or as astype(float16) (HALF).  ZIP, ZIPS and NONE run on the device; RLE goes through the
-    host writer.  The buffers grow to the largest batch seen, are reused across calls and given back by release()."""
-    time_launches = False                                       # measurements: keep (start, end) events of the launches in pack_events / deflate_events
+class DeviceEncoder(BatchEncoder):
+    """fp32 device planes to EXR files, all files of a call in one batch (batch_encode.py: BatchEncoder): one dd_exr_pack launch, one
+    dd_exr_deflate launch, one synchronisation to read statuses and sizes, a second dd_exr_pack launch (coded = 0) for exactly the chunks that
+    did not shrink, written straight into their slots, one download into a pinned buffer, and the files written on `threads` threads (at
+    most 16).  The planes read back bit-identical through read_image (FLOAT) or as astype(float16) (HALF).  ZIP, ZIPS and NONE run on the
+    device; RLE goes through the host writer."""
+    _files = "EXR"
 
     def __init__(self, device, compression=ZIP_COMPRESSION, threads=4):
-        import torch
-        self.device = torch.device(device)
         if compression not in _LINES:
             raise ExrError("cannot write compression %s" % _CODEC_NAMES.get(compression, compression))
-        if self.device.type != "cuda":
-            raise ValueError("EXR files are encoded on a GPU: %s is none" % (self.device,))
-        if self.device.index is None:
-            self.device = torch.device("cuda", torch.cuda.current_device())
+        super().__init__(device, threads)
         self.compression = compression
-        self.threads = max(1, min(int(threads), 16))
-        self._packed = self._out = self._workspace = self._tables = self._pinned = self._pinned_tables = None
-        self.pack_launches = self.deflate_launches = self.raw_chunks = self.downloaded_bytes = 0
-        self.host_seconds = 0.0                                 # wall time encode() spent assembling and writing the files
-        self.pack_events, self.deflate_events = [], []
-
-    def release(self):
-        """Give the device and the pinned buffers back (the counters stay)."""
-        import torch
-        torch.cuda.synchronize(self.device)
-        self._packed = self._out = self._workspace = self._tables = self._pinned = self._pinned_tables = None
-
-    def _grow(self, name, nbytes, pinned=False):
-        import torch
-        have = getattr(self, name)
-        if have is None or have.numel() < nbytes:
-            have = torch.empty(nbytes, dtype=torch.uint8, pin_memory=True) if pinned else torch.empty(nbytes, dtype=torch.uint8, device=self.device)
-            setattr(self, name, have)
-        return have
+        self.raw_chunks = 0
 
     def encode(self, requests):
         """requests: [(path, fp32 tensor [H,W,3] (written as R, G, B) or [H,W] (as Y) on the device, "float" / "half"), ...] -> the paths."""
-        import torch
         requests = [(path, image, _pixel_type(kind)) for path, image, kind in requests]
         if self.compression == RLE_COMPRESSION:                 # the run-length coder stays on the host
             for path, image, kind in requests:
@@ -190,16 +162,18 @@ class DeviceEncoder:
             return []
         planes, plans = [], []
         for path, image, kind in requests:
-            if not torch.is_tensor(image) or image.device != self.device or image.dtype != torch.float32:
-                raise ValueError("%s: the encoder takes fp32 tensors on %s" % (path, self.device))
+            planes.append(self._plane(path, image))
             names = _image_channels(image.shape)
-            planes.append(image.detach().contiguous())
             plans.append(plan_write(path, image.shape[0], image.shape[1], names, [kind] * len(names), self.compression))
         layout = _tables_layout(plans)
         host = self._grow("_pinned_tables", layout["bytes"], pinned=True).numpy()
         chunk_table = _fill_tables(host, layout, plans, [plane.data_ptr() for plane in planes], [1 if plane.dim() == 2 else plane.shape[2] for plane in planes])
         statuses, sizes = self._launches(layout, host, chunk_table, plans[0].coded)
-        return self._write(plans, layout, statuses, sizes)
+
+        def assemble_one(k, slots):
+            first, last = layout["first_chunk"][k], layout["first_chunk"][k] + len(plans[k].chunks)
+            return assemble(plans[k], None if statuses is None else statuses[first:last], None if sizes is None else sizes[first:last], slots)
+        return self._write(plans, layout, assemble_one)
 
     def _launches(self, layout, host, chunk_table, coded):
         """Everything on the device, for tables already filled in the pinned `host`: upload of the tables, pack, deflate, the one
@@ -213,60 +187,29 @@ class DeviceEncoder:
             out = self._grow("_out", total)
             tables = self._grow("_tables", layout["bytes"])
 
-            def upload(at, nbytes):
-                tables[at:at + nbytes].copy_(self._pinned_tables[at:at + nbytes], non_blocking=True)
-
             def pack(chunks_at, count, destination):
-                timed(self.time_launches, self.pack_events, stream, lambda: L.check(lib.dd_exr_pack(
+                self._pack(stream, lambda: lib.dd_exr_pack(
                     host[chunks_at:].ctypes.data, tables.data_ptr() + chunks_at, count, host[sources_at:].ctypes.data, tables.data_ptr() + sources_at,
-                    layout["n_files"], destination.data_ptr(), total, stream.cuda_stream)))
-                self.pack_launches += 1
-            upload(0, layout["bytes"])
+                    layout["n_files"], destination.data_ptr(), total, stream.cuda_stream))
+            self._upload(0, layout["bytes"])
             statuses = sizes = None
             if coded:
                 packed = self._grow("_packed", total)
                 workspace_bytes = int(lib.dd_exr_deflate_workspace(n_chunks))
                 workspace = self._grow("_workspace", workspace_bytes)
                 pack(0, n_chunks, packed)
-                both = torch.empty(2 * n_chunks, dtype=torch.int32, device=self.device)
-                timed(self.time_launches, self.deflate_events, stream, lambda: L.check(lib.dd_exr_deflate(
+                statuses, sizes = self._deflate(stream, n_chunks, 2, lambda status_at, sizes_at: lib.dd_exr_deflate(
                     host[streams_at:].ctypes.data, tables.data_ptr() + streams_at, n_chunks, packed.data_ptr(), total, out.data_ptr(), total,
-                    workspace.data_ptr(), workspace_bytes, both.data_ptr(), both.data_ptr() + 4 * n_chunks, stream.cuda_stream)))
-                self.deflate_launches += 1
-                both = both.cpu().numpy()                           # the one synchronisation
-                statuses, sizes = both[:n_chunks], both[n_chunks:]
+                    workspace.data_ptr(), workspace_bytes, status_at, sizes_at, stream.cuda_stream))
                 raw = np.flatnonzero(statuses == DEFLATE_RAW)
                 if len(raw):
                     redo = host[redo_at:redo_at + len(raw) * CHUNK_DTYPE.itemsize].view(CHUNK_DTYPE)
                     redo[:] = chunk_table[raw]
                     redo["coded"] = 0
-                    upload(redo_at, len(raw) * CHUNK_DTYPE.itemsize)
+                    self._upload(redo_at, len(raw) * CHUNK_DTYPE.itemsize)
                     pack(redo_at, len(raw), out)
                     self.raw_chunks += len(raw)
             else:
                 pack(0, n_chunks, out)
-            pinned = self._grow("_pinned", total, pinned=True)
-            pinned[:total].copy_(out[:total], non_blocking=True)
-            stream.synchronize()
-            self.downloaded_bytes += total
+            self._download(stream, total)
         return statuses, sizes
-
-    def _write(self, plans, layout, statuses, sizes):
-        """assemble every file from its slots in _pinned and write it, on the threads -> the paths"""
-        import concurrent.futures
-        import time
-        t0 = time.perf_counter()
-        slots = self._pinned.numpy()
-
-        def write(k):
-            p, base, first = plans[k], layout["bases"][k], layout["first_chunk"][k]
-            last = first + len(p.chunks)
-            data = assemble(p, None if statuses is None else statuses[first:last], None if sizes is None else sizes[first:last],
-                            slots[base:base + p.slot_bytes])
-            with open(p.path, "wb") as f:
-                f.write(data)
-            return p.path
-        with concurrent.futures.ThreadPoolExecutor(max_workers=self.threads) as pool:
-            written = list(pool.map(write, range(len(plans))))
-        self.host_seconds += time.perf_counter() - t0
-        return written

@@ -1,8 +1,10 @@
 """The device records of the EXR kernels as numpy dtypes, taken from the ctypes mirrors of include/dd_hip.h in _lib.py, and the two things
-the decoder and the encoder do alike with them: fill a per-file row, and run a launch between optional timing events."""
+the decoder and the encoder do alike with them: fill a per-file row, and (batch_encode.py, under the names used here) align a chunk's offset
+and run a launch between optional timing events."""
 import numpy as np
 
 from .. import _lib
+from ..batch_encode import ALIGN as _STAGE_ALIGN, align16 as _align, timed  # noqa: F401
 
 CHUNK_DTYPE = np.dtype(_lib.ExrChunk)                           # dd_exr_chunk
 FILE_DTYPE = np.dtype(_lib.ExrFile)                             # dd_exr_file
@@ -12,11 +14,6 @@ DEFLATE_STREAM_DTYPE = np.dtype(_lib.ExrDeflateStream)          # dd_exr_deflate
 MAX_FILE_CHANNELS = _lib.EXR_MAX_CHANNELS
 MAX_STREAM_BYTES = _lib.EXR_MAX_STREAM_BYTES
 DEFLATE_OK, DEFLATE_RAW, DEFLATE_RECORD = _lib.DEFLATE_OK, _lib.DEFLATE_RAW, _lib.DEFLATE_RECORD
-_STAGE_ALIGN = 16                                               # a chunk's offset in a staged buffer; it owns the bytes up to the next multiple
-
-
-def _align(n):
-    return (n + _STAGE_ALIGN - 1) // _STAGE_ALIGN * _STAGE_ALIGN
 
 
 def fill_row(table, slot, plane, height, width, channels, types, per_channel):
@@ -30,13 +27,3 @@ def fill_row(table, slot, plane, height, width, channels, types, per_channel):
     row["type"][:len(types)] = types
     row[last][:len(types)] = per_channel
 
-
-def timed(keep, events, stream, launch):
-    """Run `launch()`; with `keep` (a class's time_launches) between a (start, end) pair of timing events on `stream`, appended to `events`."""
-    if not keep:
-        return launch()
-    import torch
-    events.append((torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)))
-    events[-1][0].record(stream)
-    launch()
-    events[-1][1].record(stream)

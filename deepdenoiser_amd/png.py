@@ -25,8 +25,8 @@ import zlib
 import numpy as np
 
 from . import _lib as L
+from .batch_encode import BatchEncoder, align16 as _align, slot_layout
 from .metrics import preview_thresholds
-from .openexr.records import timed
 from .summaries import PNG_SIGNATURE, _png_chunk
 
 IMAGE_DTYPE = np.dtype(L.PngImage)                               # dd_png_image
@@ -36,16 +36,11 @@ DEFLATE_OK, DEFLATE_RAW, DEFLATE_RECORD = L.DEFLATE_OK, L.DEFLATE_RAW, L.DEFLATE
 MAX_ROW_BYTES, STAGE_BYTES = L.PNG_MAX_ROW_BYTES, L.PNG_STAGE_BYTES
 SEGMENT_TARGET_BYTES = 32768                                     # the default segment: the fewest rows whose filtered bytes reach this
 STORED_BLOCK_BYTES = 65535
-_ALIGN = 16
 _ADLER = 65521
 
 
 class PngError(ValueError):
     pass
-
-
-def _align(n):
-    return (n + _ALIGN - 1) // _ALIGN * _ALIGN
 
 
 # ---------------------------------------------------------------------------------------------------- the picture, in numpy
@@ -220,13 +215,8 @@ def assemble_png(plan, statuses, sizes, adlers, slots, staged=None):
 def _tables_layout(plans):
     """Where everything of a batch lies: the slot bytes of the files follow one another, so do their segments in the tables; the tables
     buffer holds segments | images | streams."""
-    bases, first, at, n = [], [], 0, 0
-    for p in plans:
-        bases.append(at)
-        first.append(n)
-        at += p.slot_bytes
-        n += len(p.segments)
-    layout = {"bases": bases, "first": first, "total": max(at, _ALIGN), "n_segments": n, "n_images": len(plans)}
+    bases, first, total, n = slot_layout(plans, lambda p: len(p.segments))
+    layout = {"bases": bases, "first": first, "total": total, "n_segments": n, "n_images": len(plans)}
     layout["images_at"] = _align(n * SEGMENT_DTYPE.itemsize)
     layout["streams_at"] = _align(layout["images_at"] + len(plans) * IMAGE_DTYPE.itemsize)
     layout["bytes"] = layout["streams_at"] + n * STREAM_DTYPE.itemsize
@@ -249,54 +239,30 @@ def fill_tables(host, layout, plans, pointers, plane_channels, exposures, src_ch
     return segment_table, image_table, stream_table
 
 
-class DevicePngEncoder:
-    """fp32 device planes to PNG files, all files of a call in one batch: one upload of the tables, one dd_png_pack launch, one dd_png_deflate
-    launch, one synchronisation to read statuses, sizes and Adler-32 values, the filtered bytes of the segments that did not shrink copied
-    into their slots on the device, one download into a pinned buffer, and the files assembled and written on `threads` threads (at most
-    16).  The buffers grow to the largest batch seen, are reused across calls and given back by release()."""
-    time_launches = False                                       # measurements: keep (start, end) events of the launches in pack_events / deflate_events
+class DevicePngEncoder(BatchEncoder):
+    """fp32 device planes to PNG files, all files of a call in one batch (batch_encode.py: BatchEncoder): one upload of the tables, one
+    dd_png_pack launch, one dd_png_deflate launch, one synchronisation to read statuses, sizes and Adler-32 values, the filtered bytes of the
+    segments that did not shrink copied into their slots on the device, one download into a pinned buffer, and the files assembled and
+    written on `threads` threads (at most 16)."""
+    _files = "PNG"
+    _buffers = BatchEncoder._buffers + ("_thresholds",)
 
     def __init__(self, device, threads=4, segment_rows=None):
-        import torch
-        self.device = torch.device(device)
-        if self.device.type != "cuda":
-            raise ValueError("PNG files are encoded on a GPU: %s is none" % (self.device,))
-        if self.device.index is None:
-            self.device = torch.device("cuda", torch.cuda.current_device())
-        self.threads = max(1, min(int(threads), 16))
+        super().__init__(device, threads)
         self.segment_rows = segment_rows
-        self._packed = self._out = self._workspace = self._tables = self._pinned = self._pinned_tables = self._thresholds = None
-        self.pack_launches = self.deflate_launches = self.raw_segments = self.downloaded_bytes = self.segments = 0
+        self.raw_segments = self.segments = 0
         self.staged_bytes = self.body_bytes = 0                 # what the last encode() gave deflate and what it kept of it
-        self.host_seconds = 0.0                                 # wall time encode() spent assembling and writing the files
-        self.pack_events, self.deflate_events = [], []
-
-    def release(self):
-        """Give the device and the pinned buffers back (the counters stay)."""
-        import torch
-        torch.cuda.synchronize(self.device)
-        self._packed = self._out = self._workspace = self._tables = self._pinned = self._pinned_tables = self._thresholds = None
-
-    def _grow(self, name, nbytes, pinned=False):
-        import torch
-        have = getattr(self, name)
-        if have is None or have.numel() < nbytes:
-            have = torch.empty(nbytes, dtype=torch.uint8, pin_memory=True) if pinned else torch.empty(nbytes, dtype=torch.uint8, device=self.device)
-            setattr(self, name, have)
-        return have
 
     def encode(self, requests):
         """requests: [(path, fp32 tensor [H, W, 3] (RGB), [H, W, 1] or [H, W] (gray) on the device, exposure), ...] -> the paths."""
-        import torch
         if not requests:
             return []
         planes, plans, exposures = [], [], []
         for path, image, exposure in requests:
-            if not torch.is_tensor(image) or image.device != self.device or image.dtype != torch.float32:
-                raise ValueError("%s: the encoder takes fp32 tensors on %s" % (path, self.device))
+            plane = self._plane(path, image)
             if image.dim() not in (2, 3) or (image.dim() == 3 and image.shape[2] not in (1, 3)):
                 raise PngError("%s: a pass of shape [H, W], [H, W, 1] or [H, W, 3] is expected, not %s" % (path, tuple(image.shape)))
-            planes.append(image.detach().contiguous())
+            planes.append(plane)
             n = 1 if image.dim() == 2 else image.shape[2]
             plans.append(plan_png(path, image.shape[0], image.shape[1], n, self.segment_rows))
             exposures.append(float(exposure))
@@ -304,7 +270,11 @@ class DevicePngEncoder:
         host = self._grow("_pinned_tables", layout["bytes"], pinned=True).numpy()
         fill_tables(host, layout, plans, [p.data_ptr() for p in planes], [p.n_channels for p in plans], exposures)
         statuses, sizes, adlers = self._launches(layout, host)
-        return self._write(plans, layout, statuses, sizes, adlers)
+
+        def assemble_one(k, slots):
+            first, last = layout["first"][k], layout["first"][k] + len(plans[k].segments)
+            return assemble_png(plans[k], statuses[first:last], sizes[first:last], adlers[first:last], slots)
+        return self._write(plans, layout, assemble_one)
 
     def _launches(self, layout, host):
         """Everything on the device, for tables already filled in the pinned `host` -> (statuses, sizes, adlers) per segment; the slots are
@@ -318,20 +288,16 @@ class DevicePngEncoder:
                 self._thresholds = torch.from_numpy(preview_thresholds()).to(self.device)
             out, packed = self._grow("_out", total), self._grow("_packed", total)
             tables = self._grow("_tables", layout["bytes"])
-            tables[:layout["bytes"]].copy_(self._pinned_tables[:layout["bytes"]], non_blocking=True)
+            self._upload(0, layout["bytes"])
             workspace_bytes = int(lib.dd_png_deflate_workspace(n))
             workspace = self._grow("_workspace", workspace_bytes)
-            timed(self.time_launches, self.pack_events, stream, lambda: L.check(lib.dd_png_pack(
+            self._pack(stream, lambda: lib.dd_png_pack(
                 host.ctypes.data, tables.data_ptr(), n, host[images_at:].ctypes.data, tables.data_ptr() + images_at, layout["n_images"],
-                self._thresholds.data_ptr(), packed.data_ptr(), total, stream.cuda_stream)))
-            self.pack_launches += 1
-            three = torch.empty(3 * n, dtype=torch.int32, device=self.device)
-            timed(self.time_launches, self.deflate_events, stream, lambda: L.check(lib.dd_png_deflate(
+                self._thresholds.data_ptr(), packed.data_ptr(), total, stream.cuda_stream))
+            statuses, sizes, adlers = self._deflate(stream, n, 3, lambda status_at, sizes_at, adler_at: lib.dd_png_deflate(
                 host[streams_at:].ctypes.data, tables.data_ptr() + streams_at, n, packed.data_ptr(), total, out.data_ptr(), total,
-                workspace.data_ptr(), workspace_bytes, three.data_ptr(), three.data_ptr() + 4 * n, three.data_ptr() + 8 * n, stream.cuda_stream)))
-            self.deflate_launches += 1
-            three = three.cpu().numpy()                             # the one synchronisation
-            statuses, sizes, adlers = three[:n], three[n:2 * n], three[2 * n:].view(np.uint32)
+                workspace.data_ptr(), workspace_bytes, status_at, sizes_at, adler_at, stream.cuda_stream))
+            adlers = adlers.view(np.uint32)
             stream_table = host[streams_at:streams_at + n * STREAM_DTYPE.itemsize].view(STREAM_DTYPE)
             raw = np.flatnonzero(statuses == DEFLATE_RAW)
             k = 0
@@ -343,34 +309,12 @@ class DevicePngEncoder:
                 end = int(stream_table["src_offset"][raw[j]]) + _align(int(stream_table["src_bytes"][raw[j]]))
                 out[start:end].copy_(packed[start:end], non_blocking=True)
                 k = j + 1
-            pinned = self._grow("_pinned", total, pinned=True)
-            pinned[:total].copy_(out[:total], non_blocking=True)
-            stream.synchronize()
+            self._download(stream, total)
             self.raw_segments += len(raw)
             self.segments += n
-            self.downloaded_bytes += total
             self.staged_bytes = int(stream_table["src_bytes"].sum())
             self.body_bytes = int(sizes.sum()) + int(stream_table["src_bytes"][raw].sum())
         return statuses, sizes, adlers
-
-    def _write(self, plans, layout, statuses, sizes, adlers):
-        """assemble every file from its slots in _pinned and write it, on the threads -> the paths"""
-        import concurrent.futures
-        import time
-        t0 = time.perf_counter()
-        slots = self._pinned.numpy()
-
-        def write(k):
-            p, base, first = plans[k], layout["bases"][k], layout["first"][k]
-            last = first + len(p.segments)
-            data = assemble_png(p, statuses[first:last], sizes[first:last], adlers[first:last], slots[base:base + p.slot_bytes])
-            with open(p.path, "wb") as f:
-                f.write(data)
-            return p.path
-        with concurrent.futures.ThreadPoolExecutor(max_workers=self.threads) as pool:
-            written = list(pool.map(write, range(len(plans))))
-        self.host_seconds += time.perf_counter() - t0
-        return written
 
 
 # ---------------------------------------------------------------------------------------------------- predictions and the command line
